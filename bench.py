@@ -10,7 +10,10 @@ dealt round-robin to the ranks, each rank renders its tiles at full spp, one sum
     python bench.py                      # 1 GPU
     python bench.py --gpus 8             # starts 8 ranks itself (children, before this process touches a GPU)
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8    # or under an outside launcher
+    python bench.py --full               # also: rooflines (one instrumented render), BASELINE configs 3-5, CPU baseline
+    python bench.py --dump-outputs DIR   # also: the last timed step's framebuffer as DIR/frame.npy (float32)
 
+A plain run sets up, warms up, times --steps renders and prints the headline; everything else is behind --full.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -123,6 +126,25 @@ def cpu_baseline(scene_xml, seconds_budget=12.0):
                     "linked here (libembree3.so.3 is absent); Embree's SIMD traversal would be faster than this"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """The framebuffer a caller of the timed path receives, as out_dir/frame.npy (float32, (h, w, 3)).  A frame over
+    DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its pixels instead: frame.npy (k, 3) and pixels.npy (k,), the
+    flat pixel indices y * w + x (float64, which holds them exactly)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.ascontiguousarray(frame, dtype=np.float32)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        flat = a.reshape(-1, a.shape[-1])
+        k = DUMP_LIMIT_BYTES // 2 // (flat.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=k, replace=False))
+        np.save(os.path.join(out_dir, "pixels.npy"), idx.astype(np.float64))
+        a = flat[idx]
+    np.save(os.path.join(out_dir, "frame.npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -164,6 +186,8 @@ def dry_launch(args, rank, world):
     ok = True
     if rank == 0:
         ok = bool(np.array_equal(part.numpy(), want))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, part.numpy())
         print(json.dumps({"metric": "dry launch (no rendering)", "value": None, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(elapsed / max(args.steps, 1) * 1e3, 3), "dry_launch": True, "reduce_exact": ok,
                           "config": {"workload": "tile-ownership pattern 512x512", "parallelism": f"tiles%{world}", "collective": "gloo reduce(sum) of the float framebuffer"}}), flush=True)
@@ -180,12 +204,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--scene", default=os.path.join(ROOT, "scenes", "cbox", "cbox.xml"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip BASELINE.json configs 3-5 after the headline loop")
-    ap.add_argument("--config-steps", type=int, default=2, help="timed renders per extra configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also measure the rooflines (one instrumented render per workload), BASELINE.json configs 3-5 "
+                         "and the CPU baseline; a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip BASELINE.json configs 3-5 after the headline loop")
+    ap.add_argument("--config-steps", type=int, default=2, help="with --full: timed renders per extra configuration")
     ap.add_argument("--pool", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the framebuffer of the last timed step to DIR/frame.npy (float32)")
     ap.add_argument("--dry-launch", action="store_true", help="CPU/gloo rehearsal of the N-rank launch, reduce and report; renders nothing")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -219,9 +249,10 @@ def main():
     assert stream.cuda_stream != 0
     PEAK_GWINST = 1024 * 2.4 / 2   # 256 CUs x 4 SIMD-32, one wave64 instruction per 2 cycles, 2.4 GHz (MI355X_MICROARCH.md)
 
-    def measure(scene_xml, spp, steps, warmup):
-        """`steps` timed renders of one workload (barrier + synchronize on both sides, max over ranks), then one instrumented render
-        (flags=1: HIP events around every launch, outside the timed region) for the per-kernel durations.  Returns the line's pieces."""
+    def measure(scene_xml, spp, steps, warmup, instrument, keep_frame=False):
+        """`steps` timed renders of one workload (barrier + synchronize on both sides, max over ranks), then, with `instrument`, one
+        instrumented render (flags=1: HIP events around every launch, outside the timed region) for the per-kernel durations.  With
+        `keep_frame`, the last timed step's framebuffer comes back as a host array.  Returns the line's pieces."""
         hs = lj.parse_scene(scene_xml)
         scene = lj.Scene(ctx, hs)
         w, h = hs.width, hs.height
@@ -245,6 +276,13 @@ def main():
         elapsed = ljdist.max_over_ranks(time.perf_counter() - t0, device=dev)
         ms_per_step = elapsed / steps * 1e3
         st = scene.stats()
+        name = os.path.basename(scene_xml)
+        m = {"hs": hs, "name": name, "spp": spp, "w": w, "h": h, "total_samples": total_samples, "ms_per_step": ms_per_step,
+             "value": total_samples * steps / elapsed / 1e6, "k_mean": st.bounce_iterations / max(st.samples, 1)}
+        if keep_frame:   # (before the instrumented render below writes into `frame` again)
+            m["frame"] = frame.cpu().numpy()
+        if not instrument:
+            return m
         lj.render_device(scene, frame.data_ptr(), stream=stream.cuda_stream, spp=spp, rank=rank, world_size=world, pool_paths=args.pool, flags=1)
         torch.cuda.synchronize(dev)
         si = scene.stats()
@@ -255,10 +293,8 @@ def main():
         else:
             kernels = {"k_extend": {"ms": si.extend_ms, "launches": si.extend_launches, "bytes": si.extend_bytes},
                        "k_shade": {"ms": si.shade_ms, "launches": si.shade_launches, "bytes": si.shade_bytes}}
-        name = os.path.basename(scene_xml)
-        return {"hs": hs, "name": name, "spp": spp, "w": w, "h": h, "total_samples": total_samples, "ms_per_step": ms_per_step,
-                "value": total_samples * steps / elapsed / 1e6, "k_mean": st.bounce_iterations / max(st.samples, 1), "kernels": kernels, "si": si,
-                "share": si.samples / max(total_samples, 1)}   # this rank's share of the frame's samples (1 at N = 1)
+        m.update(kernels=kernels, si=si, share=si.samples / max(total_samples, 1))   # share: this rank's share of the frame's samples (1 at N = 1)
+        return m
 
     def kernel_roofline(m, k, prof):
         """One kernel of one workload against the resource that bounds it.  k_shade streams the path queue: algorithmic HBM bytes per
@@ -297,21 +333,25 @@ def main():
         dom = max(m["kernels"], key=lambda k: m["kernels"][k]["ms"])
         return dom, out, why
 
-    m = measure(args.scene, args.spp, args.steps, args.warmup)
-    dom, rl, why_not = workload_rooflines(m)
-    roofline = dict(rl[dom])
-    whole_gbs = (m["si"].extend_bytes + m["si"].shade_bytes + m["si"].mega_bytes) / (m["ms_per_step"] * 1e-3) / 1e9
-    roofline.update({"traffic_source": (profiled_counters_source() if why_not is None else why_not),
-                     "all_kernels": {k: {"total_ms": round(v["ms"], 3), "launches": int(v["launches"]), "bound": rl[k]["bound"], "frac": rl[k]["frac"]} for k, v in m["kernels"].items()},
-                     "whole_step_GBps": round(whole_gbs, 2), "whole_step_frac": round(whole_gbs / PEAK_HBM_GBS, 5)})
+    m = measure(args.scene, args.spp, args.steps, args.warmup, args.full, keep_frame=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["frame"])
+    roofline = None
+    if args.full:
+        dom, rl, why_not = workload_rooflines(m)
+        roofline = dict(rl[dom])
+        whole_gbs = (m["si"].extend_bytes + m["si"].shade_bytes + m["si"].mega_bytes) / (m["ms_per_step"] * 1e-3) / 1e9
+        roofline.update({"traffic_source": (profiled_counters_source() if why_not is None else why_not),
+                         "all_kernels": {k: {"total_ms": round(v["ms"], 3), "launches": int(v["launches"]), "bound": rl[k]["bound"], "frac": rl[k]["frac"]} for k, v in m["kernels"].items()},
+                         "whole_step_GBps": round(whole_gbs, 2), "whole_step_frac": round(whole_gbs / PEAK_HBM_GBS, 5)})
 
     # ---- the other single-GPU configurations of BASELINE.json (3: disney_bsdf 256 spp, 4: veach_mi 512 spp, 5: sponza 1024 spp), a few
     # steps each, after the headline loop and outside its timed region; same timing discipline, reported under "configs"
     configs = []
     is_headline = os.path.basename(args.scene) == "cbox.xml" and args.spp == 256
-    if is_headline and not args.no_configs:
+    if args.full and is_headline and not args.no_configs:
         for rel, spp_c in (("disney_bsdf_test/disney_bsdf.xml", 256), ("veach_mi/mi.xml", 512), ("sponza/sponza.xml", 1024)):
-            mc = measure(os.path.join(ROOT, "scenes", rel), spp_c, args.config_steps, 1)
+            mc = measure(os.path.join(ROOT, "scenes", rel), spp_c, args.config_steps, 1, True)
             dom_c, rl_c, why_c = workload_rooflines(mc)
             e = {"workload": f"{mc['name']} {mc['w']}x{mc['h']} @ {spp_c} spp", "samples_per_step": mc["total_samples"], "steps": args.config_steps,
                  "ms_per_step": round(mc["ms_per_step"], 3), "value": round(mc["value"], 2), "unit": "Msamples/s",
@@ -335,11 +375,12 @@ def main():
                        "samples_per_step": m["total_samples"], "mean_bounce_iterations_K": round(m["k_mean"], 4),
                        "rng": "pcg32, one stream per (pixel, sample), seed 0x853c49e6748fea9b",
                        "parallelism": f"tiles%{world}" if world > 1 else "1 GPU", "collective": "RCCL reduce(sum) of the float framebuffer" if world > 1 else "none"},
-            "roofline": roofline,
         }
+        if roofline:
+            out["roofline"] = roofline
         if configs:
             out["configs"] = configs
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.scene)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -42,3 +42,30 @@ def test_single_rank_dry_launch_needs_no_process_group():
     assert r.returncode == 0, r.stderr
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["reduce_exact"] is True
+
+
+def test_dump_outputs_writes_the_reduced_frame(tmp_path):
+    """--dump-outputs DIR: rank 0's reduced frame of the last timed step lands in DIR/frame.npy, float32, bit for bit."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path)], env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = np.load(tmp_path / "frame.npy")
+    want = np.arange(512 * 512 * 3, dtype=np.float32).reshape(512, 512, 3) + 1.0
+    assert got.dtype == np.float32 and np.array_equal(got, want)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["frame.npy"]
+
+
+def test_dump_outputs_samples_a_frame_over_the_size_limit(tmp_path, monkeypatch):
+    """A frame larger than the limit is written as a seeded sample of its pixels, the same one every time."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    frame = np.random.default_rng(1).random((64, 48, 3), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    a, idx = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "pixels.npy")
+    assert a.nbytes + idx.nbytes <= 4096 and a.shape == (idx.shape[0], 3) and idx.shape[0] > 0
+    assert np.array_equal(a, frame.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(a, np.load(tmp_path / "b" / "frame.npy")) and np.array_equal(idx, np.load(tmp_path / "b" / "pixels.npy"))

@@ -4,7 +4,7 @@
 #   LJ_VARIANT=<name> LJ_EXTRA_HIPCC_FLAGS="..." python -m lajolla_public_amd.build
 # ("default" = the shipped build).  Prints ms per render (bench.py, 5 steps, no CPU baseline) per variant, two rounds interleaved.
 SCENE=$1; SPP=$2; shift 2
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline --spp $SPP"
+ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --spp $SPP"
 [ "$SCENE" != "-" ] && ARGS="$ARGS --scene $SCENE"
 for round in 1 2; do
   for v in "$@"; do

@@ -7,7 +7,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
 R="python3 tools/render_once.py scenes/cbox/cbox.xml 256 1"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02_stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/r02_bench_under_rocprof.json 2> $O/r02_bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02_stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $O/r02_bench_under_rocprof.json 2> $O/r02_bench_under_rocprof.err
 cp $O/r02_stats/*/*kernel_stats.csv $O/r02_bench_kernel_stats.csv && cut -c1-150 $O/r02_bench_kernel_stats.csv | head -8 && echo "stats done" &&
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/r02_pmc_fetch -- $R > /dev/null 2>&1 &&
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/r02_pmc_write -- $R > /dev/null 2>&1 &&
@@ -53,10 +53,10 @@ json.dump(out, open("gpurun_out/r02_counters.json", "w"), indent=1, sort_keys=Tr
 print(json.dumps({k: {x: e[x] for x in ("launches", "fetch_bytes", "write_bytes", "valu_issue_frac", "valu_active_lane_frac") if x in e} for k, e in out["kernels"].items()}, indent=1))
 PY
 cp $O/r02_counters.json profiles/r02_counters.json 2>/dev/null   # so that the bench lines below quote them (same sources, same box)
-timeout -k 10 400 python3 bench.py > $O/r02_bench_default_line.json 2> $O/r02_bench_default.err && echo "default bench done" && cut -c1-260 $O/r02_bench_default_line.json &&
+timeout -k 10 400 python3 bench.py --full > $O/r02_bench_default_line.json 2> $O/r02_bench_default.err && echo "default bench done" && cut -c1-260 $O/r02_bench_default_line.json &&
 : > $O/r02_bench_configs_3_4_5.jsonl &&
 for c in disney_bsdf_test/disney_bsdf.xml:256 veach_mi/mi.xml:512 sponza/sponza.xml:1024; do
-  timeout -k 10 300 python3 bench.py --scene scenes/${c%%:*} --spp ${c##*:} --steps 3 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/r02_bench_configs_3_4_5.jsonl && echo "config ${c%%:*} done" || exit 1
+  timeout -k 10 300 python3 bench.py --full --scene scenes/${c%%:*} --spp ${c##*:} --steps 3 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/r02_bench_configs_3_4_5.jsonl && echo "config ${c%%:*} done" || exit 1
 done
 cut -c1-200 $O/r02_bench_configs_3_4_5.jsonl
 cp profiles/r02_counters.json $O/r02_counters_copy.json 2>/dev/null

@@ -7,7 +7,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
 rm -rf $O/r03_stats $O/r03_pmc_*
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/r03_bench_under_rocprof.json 2> $O/r03_bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $O/r03_bench_under_rocprof.json 2> $O/r03_bench_under_rocprof.err
 cp $O/r03_stats/*/*kernel_stats.csv $O/r03_bench_kernel_stats.csv && cut -c1-150 $O/r03_bench_kernel_stats.csv | head -12 && echo "stats done" || exit 1
 SQA="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY"
 SQB="SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU"
@@ -25,5 +25,5 @@ rocprofv3 --pmc $SQB --kernel-trace --output-format csv -d $O/r03_pmc_sqb_0 -- $
 echo "pmc passes done" &&
 python3 tools/evidence_collect.py r03 cbox.xml@256 disney_bsdf.xml@256 mi.xml@512 sponza.xml@1024 hetvol.xml@64 vol_cbox_teapot.xml@64 &&
 cp $O/r03_counters.json profiles/r03_counters.json &&   # so that the bench line below quotes them (same sources, same box)
-timeout -k 10 600 python3 bench.py > $O/r03_bench_default_line.json 2> $O/r03_bench_default.err && echo "default bench done" && cut -c1-400 $O/r03_bench_default_line.json &&
-for v in hetvol vol_cbox_teapot; do timeout -k 10 300 python3 bench.py --scene scenes/volpath_test/$v.xml --spp 64 --no-cpu-baseline > $O/r03_bench_$v.json 2>> $O/r03_bench_default.err && cut -c1-200 $O/r03_bench_$v.json; done
+timeout -k 10 600 python3 bench.py --full > $O/r03_bench_default_line.json 2> $O/r03_bench_default.err && echo "default bench done" && cut -c1-400 $O/r03_bench_default_line.json &&
+for v in hetvol vol_cbox_teapot; do timeout -k 10 300 python3 bench.py --full --scene scenes/volpath_test/$v.xml --spp 64 --no-cpu-baseline > $O/r03_bench_$v.json 2>> $O/r03_bench_default.err && cut -c1-200 $O/r03_bench_$v.json; done

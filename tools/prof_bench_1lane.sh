@@ -4,7 +4,9 @@
 # configuration bench.py's instrumented roofline pass runs in.
 TAG=$1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+O=${LJ_OUT_DIR:-out}   # where the profiles and logs go (relative to the repository root)
+mkdir -p $O
 export LJ_TUNE_LANES=1 LJ_TUNE_TAIL=0
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/bench1_$TAG -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/bench1_$TAG.json 2> gpurun_out/bench1_$TAG.err
-tail -1 gpurun_out/bench1_$TAG.json | cut -c1-300
-cat gpurun_out/bench1_$TAG/*/*kernel_stats.csv | cut -c1-200
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench1_$TAG -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/bench1_$TAG.json 2> $O/bench1_$TAG.err
+tail -1 $O/bench1_$TAG.json | cut -c1-300
+cat $O/bench1_$TAG/*/*kernel_stats.csv | cut -c1-200

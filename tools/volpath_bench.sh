@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
 : > $O/r02_bench_volpath.jsonl
 for c in volpath_test1:256 volpath_test2:256 volpath_test4:256 volpath_test5:256 volpath_test6:256 hetvol:64 vol_cbox_teapot:64; do
-  timeout -k 10 300 python3 bench.py --scene scenes/volpath_test/${c%%:*}.xml --spp ${c##*:} --steps 3 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/r02_bench_volpath.jsonl || echo "FAILED $c"
+  timeout -k 10 300 python3 bench.py --full --scene scenes/volpath_test/${c%%:*}.xml --spp ${c##*:} --steps 3 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/r02_bench_volpath.jsonl || echo "FAILED $c"
 done
 python3 -c "
 import json
