@@ -196,12 +196,21 @@ void lj_context_destroy(lj_context *ctx);
 int lj_scene_upload(lj_context *ctx, const LjSceneDesc *desc, lj_scene **out);
 void lj_scene_destroy(lj_scene *scene);
 
-enum { LJ_RNG_SAMPLE = 0 /* one pcg32 stream per (pixel, sample): stream = (y*w + x)*spp + s */ };
+enum {
+    LJ_RNG_SAMPLE = 0, /* one pcg32 stream per (pixel, sample): stream = (y*w + x)*spp + s */
+    LJ_RNG_TILE = 1    /* the reference's render() schedule (render.cpp:80-96, 125-141): one pcg32 stream per 16x16 tile,
+                          stream = ty*ntx + tx (ntx = ceil(w / 16)), initialised with `seed`; each tile consumes its stream pixel by
+                          pixel, row-major inside the tile, and sample by sample, every draw of a sample before the next sample's.
+                          The only parallelism is across tiles: a fidelity mode, not a fast one.  A crop window renders
+                          every tile it touches whole and writes only its own pixels, so they are bit-identical to the same pixels of a
+                          full-frame render; LjStats.samples then counts the samples traced outside the window too.  The auxiliary
+                          integrators draw nothing: their output is the same in both modes. */
+};
 
 typedef struct LjRenderArgs {
     int32_t spp;         /* <=0: RenderOptions::samples_per_pixel */
     int32_t max_depth;   /* INT32_MIN: RenderOptions::max_depth */
-    int32_t rng_mode;    /* LJ_RNG_SAMPLE */
+    int32_t rng_mode;    /* LJ_RNG_SAMPLE or LJ_RNG_TILE; any other value: LJ_ERR_UNSUPPORTED */
     int32_t rank, world_size; /* render only the 16x16 tiles t = ty*ntx+tx with t % world_size == rank (render.cpp:75-88);
                                  other pixels are written as 0 so a sum over ranks is the full image */
     int32_t crop_x0, crop_y0, crop_x1, crop_y1; /* all 0: full frame; else only pixels in [x0,x1)x[y0,y1) */
@@ -297,7 +306,7 @@ int lj_frame_queries(lj_context *ctx, int64_t n, const LjFrameQuery *queries_hos
 
 /* Counters of the last lj_render* call. */
 typedef struct LjStats {
-    uint64_t samples;          /* camera samples traced */
+    uint64_t samples;          /* camera samples traced (LJ_RNG_TILE: those of every tile walked, outside a crop window too) */
     uint64_t bounce_iterations;/* sum over samples of executed iterations of the loop at path_tracing.h:66 (K) */
     uint64_t rays_closest, rays_shadow;
     uint64_t wavefront_steps;  /* host-side iterations of the extend/shade cycle */

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import LjRenderArgs, LjSceneDesc, LjStats, LjSceneInfo, LjRay, LjHit
+from ._abi import LJ_RNG_SAMPLE, LJ_RNG_TILE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (LJ_VARIANT: a developer build of the same library with other compile flags, see build.py; unset in every shipped path)
@@ -174,11 +175,13 @@ class Scene:
         return st
 
 
-def make_args(spp=0, max_depth=None, rank=0, world_size=1, crop=None, pool_paths=0, seed=0, flags=0):
+def make_args(spp=0, max_depth=None, rank=0, world_size=1, crop=None, pool_paths=0, seed=0, flags=0, rng_mode=_abi.LJ_RNG_SAMPLE):
+    """rng_mode: _abi.LJ_RNG_SAMPLE (one pcg32 stream per pixel sample, the default) or _abi.LJ_RNG_TILE (the reference's render()
+    schedule: one stream per 16x16 tile, consumed in order — include/lajolla_hip.h)."""
     a = LjRenderArgs()
     a.spp = int(spp)
     a.max_depth = _abi.INT32_MIN if max_depth is None else int(max_depth)
-    a.rng_mode = 0
+    a.rng_mode = int(rng_mode)
     a.rank, a.world_size = int(rank), int(world_size)
     if crop is not None:
         a.crop_x0, a.crop_y0, a.crop_x1, a.crop_y1 = [int(v) for v in crop]

@@ -1,19 +1,21 @@
-"""`python -m lajolla_public_amd [-o output_file_name] [--spp N] [--gpus N | --devices 0,1,..] filename.xml ...` — the reference's
+"""`python -m lajolla_public_amd [-o output_file_name] [--spp N] [--rng tile|sample] [--gpus N | --devices 0,1,..] filename.xml ...` — the reference's
 driver loop (main.cpp:12-51) on the HIP path: parse, render, write to `-o` or the scene's own output file name (PFM / EXR).
 `-t num_threads` is accepted and ignored (the render does not run on host threads).  `--gpus N` renders on the first N devices of
 the node from this one process (a device group: tiles sharded t % N, one RCCL reduce); `--devices` names them (ids may repeat:
-logical ranks on one GPU)."""
+logical ranks on one GPU).  `--rng tile` draws the random numbers in the reference's own order (one pcg32 stream per 16x16 tile,
+LJ_RNG_TILE: slower, for reproducing a reference render); the default `--rng sample` gives every pixel sample a stream of its own."""
 import sys
 import time
 
+from . import _abi
 from . import Context, DeviceGroup, GroupScene, Scene, parse_scene, render, render_group, write_image
 
 
 def main(argv):
     if not argv:
-        print("[Usage] python -m lajolla_public_amd [-t num_threads] [-o output_file_name] [--spp N] [--gpus N | --devices i,j,..] filename.xml")
+        print("[Usage] python -m lajolla_public_amd [-t num_threads] [-o output_file_name] [--spp N] [--rng tile|sample] [--gpus N | --devices i,j,..] filename.xml")
         return 0
-    output, spp, filenames, devices = "", 0, [], None
+    output, spp, filenames, devices, rng_mode = "", 0, [], None, _abi.LJ_RNG_SAMPLE
     i = 0
     while i < len(argv):
         if argv[i] == "-t":
@@ -24,6 +26,13 @@ def main(argv):
         elif argv[i] == "--spp":
             i += 1
             spp = int(argv[i])
+        elif argv[i] == "--rng":
+            i += 1
+            modes = {"sample": _abi.LJ_RNG_SAMPLE, "tile": _abi.LJ_RNG_TILE}
+            if argv[i] not in modes:
+                print(f"--rng: expected tile or sample, got {argv[i]!r}", file=sys.stderr)
+                return 2
+            rng_mode = modes[argv[i]]
         elif argv[i] == "--gpus":
             i += 1
             devices = list(range(int(argv[i])))
@@ -43,7 +52,7 @@ def main(argv):
         print(f"Done. Took {time.perf_counter() - t0:.6g} seconds.")
         print("Rendering...")
         t0 = time.perf_counter()
-        img = render_group(sc, spp=spp) if group else render(sc, spp=spp)
+        img = render_group(sc, spp=spp, rng_mode=rng_mode) if group else render(sc, spp=spp, rng_mode=rng_mode)
         if output == "":
             output = hs.desc.output_filename.decode()
         print(f"Done. Took {time.perf_counter() - t0:.6g} seconds.")

@@ -4,6 +4,7 @@ import ctypes as C
 LJ_OK = 0
 LJ_ERR_INVALID_ARG, LJ_ERR_PARSE, LJ_ERR_IO, LJ_ERR_UNSUPPORTED, LJ_ERR_DEVICE, LJ_ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 
+LJ_RNG_SAMPLE, LJ_RNG_TILE = 0, 1   # LjRenderArgs.rng_mode: one pcg32 stream per (pixel, sample) / per 16x16 tile (the reference's render())
 LJ_FILTER_BOX, LJ_FILTER_TENT, LJ_FILTER_GAUSSIAN = 0, 1, 2
 LJ_SHAPE_SPHERE, LJ_SHAPE_TRIMESH = 0, 1
 LJ_TEX_CONSTANT, LJ_TEX_IMAGE, LJ_TEX_CHECKERBOARD = 0, 1, 2

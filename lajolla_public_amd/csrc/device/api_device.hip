@@ -39,6 +39,8 @@ struct RenderPlan {
     std::shared_ptr<const std::vector<uint32_t>> pixels;  // rendered pixels in tile order (cached per scene: same share -> same list)
     uint64_t pixels_key = 0;                               // identifies the list on the device (lj_context::pixel_list_key)
     int max_depth;
+    int rng_mode;                                          // LJ_RNG_SAMPLE / LJ_RNG_TILE
+    int rank, world, cx0, cy0, cx1, cy1;                   // the share and the crop window (the full frame when there is none)
 };
 
 RenderPlan make_plan(const lj_scene *sc, const LjRenderArgs *a) {
@@ -53,13 +55,15 @@ RenderPlan make_plan(const lj_scene *sc, const LjRenderArgs *a) {
     // (tools/pool_big.sh, sponza 1024 spp: 2^25 828 ms, 2^26 811, 2^27 794, 2^28 793; disney_bsdf 256 spp: 97.3 / 93.4 / 91.8 / 91.5)
     p.pool = (a && a->pool_paths) ? a->pool_paths : (1u << 27);
     p.pool = std::max<uint32_t>(p.pool, 4096);
-    if (a && a->rng_mode != LJ_RNG_SAMPLE) throw LjError(LJ_ERR_UNSUPPORTED, "only LJ_RNG_SAMPLE exists on the device (a per-tile sequential stream cannot be parallelised, SURVEY §0.2)");
+    p.rng_mode = a ? a->rng_mode : LJ_RNG_SAMPLE;
+    if (p.rng_mode != LJ_RNG_SAMPLE && p.rng_mode != LJ_RNG_TILE) throw LjError(LJ_ERR_UNSUPPORTED, "rng_mode must be LJ_RNG_SAMPLE or LJ_RNG_TILE");
     int rank = a ? a->rank : 0, world = (a && a->world_size > 0) ? a->world_size : 1;
     if (rank < 0 || rank >= world) throw LjError(LJ_ERR_INVALID_ARG, "rank must be in [0, world_size)");
     bool crop = a && a->crop_x1 > a->crop_x0 && a->crop_y1 > a->crop_y0;
     int cx0 = crop ? a->crop_x0 : 0, cy0 = crop ? a->crop_y0 : 0, cx1 = crop ? a->crop_x1 : w, cy1 = crop ? a->crop_y1 : h;
     if (cx0 < 0 || cy0 < 0 || cx1 > w || cy1 > h) throw LjError(LJ_ERR_INVALID_ARG, "crop window outside the film");
     const int tile = 16, ntx = (w + tile - 1) / tile, nty = (h + tile - 1) / tile;  // render.cpp:75-77
+    p.rank = rank; p.world = world; p.cx0 = cx0; p.cy0 = cy0; p.cx1 = cx1; p.cy1 = cy1;
     // the pixel list depends on the share only (rank, world, crop): a render loop asks for the same one every frame
     const uint64_t key_parts[9] = {(uint64_t)rank, (uint64_t)world, (uint64_t)crop, (uint64_t)cx0, (uint64_t)cy0, (uint64_t)cx1, (uint64_t)cy1, (uint64_t)w, (uint64_t)h};
     uint64_t key = 1469598103934665603ull;
@@ -95,6 +99,69 @@ void upload_pixel_list(lj_context *ctx, const RenderPlan &plan, hipStream_t stre
     ctx->pixel_list_key = plan.pixels_key;
 }
 
+// The per-tile schedule (LJ_RNG_TILE, dtile.h / tile.hip) for path and volpath: every tile of the share that touches the crop window is
+// walked whole — its stream is consumed for the pixels outside the window too — and only the window's pixels are written (rgb_dev:
+// radiance / spp; samples_host: per-sample radiance in lj_render_samples layout).  Bounded launches: each advances every unfinished tile
+// by at most LJ_TUNE_TILE_STEPS path steps; the cursors stay in HBM between launches.  LjStats.samples counts every sample traced,
+// those outside the window included.
+void run_tiles(lj_scene *sc, const RenderPlan &plan, const ljd::DScene &ds, float *rgb_dev, float *samples_host, hipStream_t stream) {
+    lj_context *ctx = sc->ctx;
+    LjStats &st = sc->stats;
+    const bool vol = sc->flat.integrator == LJ_INTEGRATOR_VOLPATH;
+    const int w = sc->flat.cam.width, h = sc->flat.cam.height, T = 16;   // render.cpp:75
+    const int ntx = (w + T - 1) / T, nty = (h + T - 1) / T;
+    std::vector<uint32_t> tiles;
+    for (int t = 0; t < ntx * nty; t++) {
+        if (t % plan.world != plan.rank) continue;
+        const int x0 = (t % ntx) * T, y0 = (t / ntx) * T;
+        if (x0 < plan.cx1 && x0 + T > plan.cx0 && y0 < plan.cy1 && y0 + T > plan.cy0) tiles.push_back((uint32_t)t);
+    }
+    if (tiles.empty()) return;
+    const uint32_t n_tiles = (uint32_t)tiles.size();
+    // tiles per wave (1..64): 1 spreads the tiles over the SIMDs one by one, 64 packs them into full waves
+    uint32_t lanes = 1;
+    if (const char *e = getenv("LJ_TUNE_TILE_LANES")) lanes = (uint32_t)std::min(64, std::max(1, atoi(e)));
+    uint32_t budget = 512;   // path steps per tile and launch
+    if (const char *e = getenv("LJ_TUNE_TILE_STEPS")) budget = (uint32_t)std::max(1, atoi(e));
+    const size_t cur_bytes = ljd::tile_cursor_bytes(vol) * n_tiles;
+    if (ctx->tile_cursors.bytes < cur_bytes) ctx->tile_cursors.alloc(cur_bytes);
+    if (ctx->tile_list.bytes < (size_t)n_tiles * 4 + 64) ctx->tile_list.alloc((size_t)n_tiles * 4 + 64);
+    const uint64_t n_samples_out = samples_host ? (uint64_t)(plan.cx1 - plan.cx0) * (uint64_t)(plan.cy1 - plan.cy0) * (uint64_t)plan.spp : 0;
+    if (samples_host && ctx->tile_samples.bytes < n_samples_out * 12) ctx->tile_samples.alloc(n_samples_out * 12);
+    uint32_t *tile_ids = (uint32_t *)ctx->tile_list.p, *alive = tile_ids + ((n_tiles + 15u) & ~15u);   // (the alive counter after the list)
+    HIP_CHECK(hipMemcpyAsync(tile_ids, tiles.data(), (size_t)n_tiles * 4, hipMemcpyHostToDevice, stream));
+    ljd::DTileJob job{};
+    job.tiles = tile_ids; job.n_tiles = n_tiles; job.ntx = (uint32_t)ntx; job.spp = (uint32_t)plan.spp;
+    job.cx0 = plan.cx0; job.cy0 = plan.cy0; job.cx1 = plan.cx1; job.cy1 = plan.cy1;
+    job.seed = plan.seed; job.rgb = rgb_dev; job.samples = samples_host ? (float *)ctx->tile_samples.p : nullptr;
+    int *spill = ensure_spill(ctx, sc->ecfg.spill_levels, (uint32_t)ljd::tile_grid(n_tiles, lanes));
+    HIP_CHECK(hipEventRecord(ctx->ev_begin, stream));
+    ljd::launch_tile_init(vol, ctx->tile_cursors.p, tile_ids, n_tiles, plan.seed, stream);
+    HIP_CHECK(hipGetLastError());
+    unsigned int *h_alive = (unsigned int *)ctx->stats_host;
+    uint64_t launches = 0;
+    for (;;) {
+        HIP_CHECK(hipMemsetAsync(alive, 0, 4, stream));
+        ljd::launch_tile(vol, ds, job, ctx->tile_cursors.p, lanes, budget, alive, sc->ecfg, spill, stream);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(h_alive, alive, 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        launches++;
+        if (*h_alive == 0) break;
+        if (launches >= (1u << 24)) throw LjError(LJ_ERR_INTERNAL, "tile walk did not finish");
+    }
+    HIP_CHECK(hipEventRecord(ctx->ev_end, stream));
+    HIP_CHECK(hipEventSynchronize(ctx->ev_end));
+    float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+    std::vector<unsigned char> cur_host(cur_bytes);
+    HIP_CHECK(hipMemcpy(cur_host.data(), ctx->tile_cursors.p, cur_bytes, hipMemcpyDeviceToHost));
+    if (samples_host) HIP_CHECK(hipMemcpy(samples_host, ctx->tile_samples.p, n_samples_out * 12, hipMemcpyDeviceToHost));
+    unsigned long long c[5];
+    ljd::tile_cursor_stats(vol, cur_host.data(), n_tiles, c);
+    st.render_ms = ms; st.samples = c[0]; st.bounce_iterations = c[1]; st.rays_closest = c[2]; st.rays_shadow = c[3]; st.path_steps = c[4];
+    st.wavefront_steps = launches;
+}
+
 // Renders plan.pixels; if rgb_dev != null writes radiance/spp there (other pixels untouched), if samples_host != null
 // the per-sample radiance of every pass is copied to host memory in pixel-list order.
 void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *samples_host, hipStream_t stream, bool timing) {
@@ -119,6 +186,7 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
         st.render_ms = ms; st.samples = n_pix; st.rays_closest = n_pix;
         return;
     }
+    if (plan.rng_mode == LJ_RNG_TILE) { run_tiles(sc, plan, ds, rgb_dev, samples_host, stream); return; }   // (the auxiliary integrators draw nothing: as above)
     // pass size: keep the per-sample radiance buffer <= ~1.5 GiB and sample ids in 32 bits
     const uint64_t max_samples_pass = (uint64_t)1 << 27;
     uint64_t pix_per_pass = std::max<uint64_t>(1, max_samples_pass / (uint64_t)plan.spp);

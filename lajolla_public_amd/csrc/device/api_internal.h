@@ -34,6 +34,12 @@ size_t mega_smem(const DScene &sc, const ShadeConfig &scfg);
 int mega_blocks_per_cu(const ShadeConfig &scfg);
 void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, bool spheres, uint32_t n_samples, uint32_t grab, uint32_t *sample_counter, unsigned long long *stats, int grid, hipStream_t s);
 void launch_trace_rays_scan(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, int grid, hipStream_t s);
+// tile.hip: the per-tile schedule (LJ_RNG_TILE)
+size_t tile_cursor_bytes(bool vol);
+void launch_tile_init(bool vol, void *cursors, const uint32_t *tiles, uint32_t n_tiles, uint64_t seed, hipStream_t s);
+int tile_grid(uint32_t n_tiles, uint32_t lanes);
+void launch_tile(bool vol, const DScene &sc, const DTileJob &job, void *cursors, uint32_t lanes, uint32_t budget, uint32_t *alive, const ExtendConfig &cfg, int *spill, hipStream_t s);
+void tile_cursor_stats(bool vol, const void *cursors_host, uint32_t n, unsigned long long out[5]);
 }
 
 using lj::LjError;
@@ -74,6 +80,7 @@ struct lj_context {
     DevBuf spill;  // overflow levels of the traversal stacks: spill_levels x (grid * 256) ints
     DevBuf blocks, sample_rgb, pixel_list, frame;
     uint64_t pixel_list_key = 0;   // which pixel list `pixel_list` holds (RenderPlan::pixels_key), 0: none
+    DevBuf tile_cursors, tile_list, tile_samples;   // the per-tile schedule: one cursor per tile (dtile.h), the tile ids, per-sample radiance
     DevBuf mega_state;   // k_mega: [0] the grid-wide camera-sample counter (uint32), [8..] five 64-bit statistics
     ljd::DBlockState *blocks_host = nullptr;  // pinned, kMaxBlocks entries
     unsigned long long *stats_host = nullptr; // pinned, 8 entries: where a launch's statistics are read back (one wait per pass, no staged copy)

@@ -854,10 +854,12 @@ LJ_HD void generate_path(const DScene &sc, const DPass &pass, uint32_t sample_id
 // next (path_tracing.h:58-61 for camera rays; :239-322 tail of iteration k, then :94-237 head of iteration k+1).
 // Returns true if the path continues (ps holds the next extension + shadow rays), false if it is finished
 // (ps.rad is the value of path_tracing() for this sample).
-template <class Ft = FeatAll>
-LJ_HD bool shade_path(const DScene &sc, const DPass &pass, PathState &ps, ShadeCounters &cnt) {
-    const uint32_t pix_i = fast_div(ps.sample, pass.by_spp);
-    const uint64_t inc = pcg32_inc((uint64_t)pass.pixel_list[pix_i] * pass.spp + (ps.sample - pix_i * pass.spp));
+// `inc`: the pcg32 stream ps.rng belongs to.  DEFER_RR (the per-tile schedule, dtile.h): the Russian roulette draw of an iteration is
+// not taken when the continuation ray is sampled but at the start of the next step, and only if that ray hit something — where
+// path_tracing.h:301-317 takes it (`if (!bsdf_vertex) break;` comes first).  With one stream per sample the early draw is harmless (the
+// stream of a finished sample is thrown away); with one stream per tile it would shift every later sample of the tile.
+template <class Ft, bool DEFER_RR>
+LJ_HD bool shade_path_body(const DScene &sc, uint64_t inc, PathState &ps, ShadeCounters &cnt) {
     // pending next-event estimation of the previous vertex (path_tracing.h:207)
     if (ps.hcode & HIT_VIS_BIT) ps.rad = ps.rad + ps.nee;
     const bool primary = ps.p2 < 0.0f;
@@ -892,7 +894,8 @@ LJ_HD bool shade_path(const DScene &sc, const DPass &pass, PathState &ps, ShadeC
             ps.rad = ps.rad + ps.W * L * w2;
         }
     }
-    if (ps.flags & PF_DYING) return false;  // Russian roulette said stop (path_tracing.h:314-317)
+    if (!DEFER_RR && (ps.flags & PF_DYING)) return false;  // Russian roulette said stop (path_tracing.h:314-317)
+    if (DEFER_RR && (ps.flags & PF_RR_PENDING) && pcg32_real(ps.rng, inc) > ps.rr) return false;
     // loop header of the next iteration (path_tracing.h:66)
     const uint32_t nv = nv_prev + 1;
     if (!(sc.max_depth == -1 || (int)nv <= sc.max_depth + 1)) return false;
@@ -958,9 +961,17 @@ LJ_HD bool shade_path(const DScene &sc, const DPass &pass, PathState &ps, ShadeC
     ps.rr = 1.0f;
     if ((int)nv - 1 >= sc.rr_depth) {
         ps.rr = fminf(max3(thr * (1.0f / ps.eta_scale)), 0.95f);
-        if (pcg32_real(ps.rng, inc) > ps.rr) ps.flags |= PF_DYING;
+        if (DEFER_RR) ps.flags |= PF_RR_PENDING;
+        else if (pcg32_real(ps.rng, inc) > ps.rr) ps.flags |= PF_DYING;
     }
     return true;
+}
+// the per-(pixel, sample) schedule: the stream of sample ps.sample of the pass
+template <class Ft = FeatAll>
+LJ_HD bool shade_path(const DScene &sc, const DPass &pass, PathState &ps, ShadeCounters &cnt) {
+    const uint32_t pix_i = fast_div(ps.sample, pass.by_spp);
+    const uint64_t inc = pcg32_inc((uint64_t)pass.pixel_list[pix_i] * pass.spp + (ps.sample - pix_i * pass.spp));
+    return shade_path_body<Ft, false>(sc, inc, ps, cnt);
 }
 
 } // namespace ljd

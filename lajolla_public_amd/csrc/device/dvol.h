@@ -282,11 +282,14 @@ struct VolPath {
     float eta_scale;
     uint32_t bounce_iterations;         // (statistics: iterations that reached the scattering / shading part)
     int guard;                          // Russian roulette ends a path with probability >= 5 % per iteration past rr_depth; the cap bounds rr_depth = huge
+                                        // (the reference has no such cap: a path that reaches 65536 iterations ends here with the radiance so far —
+                                        // in the per-tile schedule the tile's stream then continues from where this path left it)
 };
 // returns false when the sample is already finished (`result`): versions 1 and 2 are single-shot estimators
+// `rng`: the stream the sample draws from, at its current position (the per-tile schedule hands over the tile's stream, dtile.h)
 template <class Ft, class Tracer>
-LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, uint64_t stream, uint64_t seed, VolPath &P, f3 &result) {
-    P.rng.inc = pcg32_inc(stream); P.rng.state = pcg32_init(stream, seed);
+LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, VolRng rng, VolPath &P, f3 &result) {
+    P.rng = rng;
     P.bounce_iterations = 0; P.guard = 0;
     if (sc.vol_path_version == 1) { result = vol_path_sample_1<Ft>(sc, tr, x, y, P.rng); return false; }
     if (sc.vol_path_version == 2) { result = vol_path_sample_2<Ft>(sc, tr, x, y, P.rng); return false; }
@@ -300,6 +303,12 @@ LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, uint64_t s
     P.multi_trans_pdf = mk3(1, 1, 1);
     P.eta_scale = 1.0f;
     return true;
+}
+// the per-(pixel, sample) schedule: a fresh stream per sample
+template <class Ft, class Tracer>
+LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, uint64_t stream, uint64_t seed, VolPath &P, f3 &result) {
+    VolRng rng; rng.inc = pcg32_inc(stream); rng.state = pcg32_init(stream, seed);
+    return vol_path_begin<Ft>(sc, tr, x, y, rng, P, result);
 }
 // one iteration of the loop; false: the path has ended with `result`
 template <class Ft, class Tracer>
