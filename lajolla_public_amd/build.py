@@ -165,6 +165,22 @@ def build_twin_tile(verbose=True):
     return TWIN_TILE_LIB
 
 
+TWIN_REGEN_LIB = os.path.join(ROOT, "tests", "twin_regen", "_build", "libljtwinregen_asan.so" if _SAN else "libljtwinregen.so")
+
+
+def build_twin_regen(verbose=True):
+    """Host model of a persistent k_mega grid over the kernel's sample bookkeeping (device/dregen.h) for the CPU-side tests."""
+    src = os.path.join(ROOT, "tests", "twin_regen", "twin_regen.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_REGEN_LIB), exist_ok=True)
+    if _stale(TWIN_REGEN_LIB, [src] + _headers()):
+        if verbose:
+            print("[build] compiling the host model of the mega kernel's sample bookkeeping (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2"] + _SAN_FLAGS + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", TWIN_REGEN_LIB, src])
+    return TWIN_REGEN_LIB
+
+
 def build_reference_subset():
     """oracle/_ref from the reference's own sources — only where /root/reference exists (this container)."""
     script = os.path.join(ROOT, "oracle", "ref_build.sh")
@@ -179,4 +195,5 @@ if __name__ == "__main__":
     if "--twin" in sys.argv or "--all" in sys.argv:
         build_twin()
         build_twin_tile()
+        build_twin_regen()
     print(LIB)

@@ -241,7 +241,7 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
         if (!ctx->mega_state.p) ctx->mega_state.alloc(64);
         upload_pixel_list(ctx, plan, stream);
         HIP_CHECK(hipEventRecord(ctx->ev_begin, stream));
-        int per_cu = ljd::mega_blocks_per_cu(sc->scfg);
+        int per_cu = ljd::mega_blocks_per_cu(sc->dscene, sc->scfg);
         if (const char *e = getenv("LJ_TUNE_MEGA_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(e));
         // camera samples a wave takes off the counter at a time: a multiple of 64 so that a wave's lanes share pixels, chosen so that
         // every wave draws ~16 times and the grid ends together — between 192 (below that the counter traffic shows) and 768:

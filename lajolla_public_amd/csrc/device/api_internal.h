@@ -31,7 +31,7 @@ int volpath_blocks_per_cu(const DScene &sc);
 void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
 // mega.hip
 size_t mega_smem(const DScene &sc, const ShadeConfig &scfg);
-int mega_blocks_per_cu(const ShadeConfig &scfg);
+int mega_blocks_per_cu(const DScene &sc, const ShadeConfig &scfg);
 void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, bool spheres, uint32_t n_samples, uint32_t grab, uint32_t *sample_counter, unsigned long long *stats, int grid, hipStream_t s);
 void launch_trace_rays_scan(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, int grid, hipStream_t s);
 // tile.hip: the per-tile schedule (LJ_RNG_TILE)

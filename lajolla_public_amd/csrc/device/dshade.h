@@ -830,7 +830,9 @@ struct PathState {
 struct ShadeCounters { uint32_t bounces, closest, shadow, done; };
 
 // Camera-sample generation: path_tracing.h:10-14 + render.cpp:82 (per-sample stream variant).
-LJ_HD void generate_path(const DScene &sc, const DPass &pass, uint32_t sample_id, PathState &ps) {
+// In two pieces so that k_mega can compute samples with all lanes of a wave and start them on other lanes later (mega.hip):
+// camera_sample — everything that depends on the sample id: the primary direction and the pcg32 state after the two jitter draws;
+LJ_HD void camera_sample(const DScene &sc, const DPass &pass, uint32_t sample_id, f3 &dir, uint64_t &rng) {
     const uint32_t p = fast_div(sample_id, pass.by_spp), s = sample_id - p * pass.spp;
     const uint32_t pixel = pass.pixel_list[p];
     const int y = (int)fast_div(pixel, pass.by_width), x = (int)(pixel - (uint32_t)y * (uint32_t)sc.cam.width);
@@ -840,14 +842,24 @@ LJ_HD void generate_path(const DScene &sc, const DPass &pass, uint32_t sample_id
     // the reference's g++ build gives the first draw to the y jitter and the second to x
     const float jy = pcg32_real(st, inc);
     const float jx = pcg32_real(st, inc);
+    dir = camera_primary_dir(sc.cam, x, y, jx, jy);
+    rng = st;
+}
+// start_path — the path record of that sample: the two values above and constants.
+LJ_HD void start_path(const DScene &sc, uint32_t sample_id, f3 dir, uint64_t rng, PathState &ps) {
     ps.org = ld3(sc.cam.org);
-    ps.dir = camera_primary_dir(sc.cam, x, y, jx, jy);
+    ps.dir = dir;
     ps.sdir = mk3(0, 0, 0); ps.stfar = 0.0f;
     ps.W = mk3(1, 1, 1); ps.rr = 1.0f; ps.p2 = -1.0f;
     ps.rad = mk3(0, 0, 0); ps.nee = mk3(0, 0, 0);
-    ps.sample = sample_id; ps.rng = st;
+    ps.sample = sample_id; ps.rng = rng;
     ps.eta_scale = 1.0f; ps.spread = sc.init_spread;
     ps.flags = 2u;  // num_vertices so far (camera + the vertex this ray will find); the first loop iteration is 3
+}
+LJ_HD void generate_path(const DScene &sc, const DPass &pass, uint32_t sample_id, PathState &ps) {
+    f3 dir; uint64_t rng;
+    camera_sample(sc, pass, sample_id, dir, rng);
+    start_path(sc, sample_id, dir, rng, ps);
 }
 
 // One wavefront step for one path: everything path_tracing() does between the return of one intersect() and the

@@ -18,13 +18,23 @@
 #include "dstage.h"
 #include "dtrace.h"
 #include "dconfig.h"
+#include "dregen.h"
 
 namespace ljd {
 
 #define LJ_CONST __attribute__((address_space(4)))   // constant address space: uniform loads become s_load (scalar cache)
 
-constexpr uint32_t kItemCap = 512;                    // (ray, leaf) candidates pooled per wave and pass
-constexpr uint32_t kWaveScanBytes = 64 * 48 + 64 * 8 + 64 * 4 + kItemCap * 2;   // rays | keys | occluded flags | items
+// (ray, leaf) candidates pooled per wave and pass: a pass stops taking rounds above the cap - 64, the rest waits for the next pass.  512,
+// except in the k_mega build that carries a camera-sample stash (below; cbox: a wave-step pools ~150, 2.3 per lane): 304 there, so that
+// its workgroup needs 31 984 B of LDS — the most that still lets five of them share a CU (kLdsPerCU in kLdsGranule steps: 32 000 B each).
+constexpr uint32_t kItemCap = 512, kItemCapTight = 304;
+constexpr uint32_t kWaveStashBytes = kRegenSlots * (8 + 12);   // a wave's generated camera samples: pcg32 states | directions (x[], y[], z[])
+// a wave's scratch: rays | keys | [stash] | occluded flags | items
+constexpr uint32_t wave_scan_bytes(uint32_t item_cap, bool stash) { return 64 * 48 + 64 * 8 + (stash ? kWaveStashBytes : 0u) + 64 + item_cap * 2; }
+static_assert(wave_scan_bytes(kItemCap, false) % 16 == 0 && wave_scan_bytes(kItemCapTight, true) % 16 == 0, "the next wave's rays are 16-byte records");
+// LDS of a gfx950 CU and the unit it is handed out in: the LLVM AMDGPU backend allocates LDS on subtargets with 160 KiB of it in granules of
+// 320 dwords (getLdsDwGranularity, AMDGPUBaseInfo.cpp; 128 dwords on the 64 KiB parts) and reports occupancy accordingly
+constexpr size_t kLdsPerCU = 160 * 1024, kLdsGranule = 320 * 4;
 
 struct ScanCtx {
     const LJ_CONST float *boxes;        // DScanLeaf records (8 dwords each), wave-uniform reads
@@ -35,8 +45,10 @@ struct ScanCtx {
     // this wave's scratch
     LJ_LDS v4f *rays;                   // [lane * 3 + {0: org | tfar_shadow, 1: dir_ext | tnear_ext, 2: dir_shadow | tnear_shadow}]; tfar_ext = inf
     LJ_LDS unsigned long long *keys;    // closest hit of lane's extension ray: float bits of t << 32 | gprim << 16 | leaf-order index
-    LJ_LDS uint32_t *occl;              // != 0: lane's shadow ray is blocked
-    LJ_LDS uint16_t *items;
+    LJ_LDS uint8_t *occl;               // != 0: lane's shadow ray is blocked
+    LJ_LDS uint16_t *items; uint32_t item_cap;
+    LJ_LDS uint64_t *st_rng;            // stash of camera samples (k_mega builds with STASH only): slot i holds sample st_base + i — its pcg32 state after the jitter draws
+    LJ_LDS float *st_dir;               // and its primary direction at [i], [64 + i], [128 + i]
 };
 
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -129,14 +141,14 @@ __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool h
     r1.x = dir_e.x; r1.y = dir_e.y; r1.z = dir_e.z; r1.w = tnear_e;
     r2.x = dir_s.x; r2.y = dir_s.y; r2.z = dir_s.z; r2.w = tnear_s;
     sx.rays[lane * 3] = r0; sx.rays[lane * 3 + 1] = r1; sx.rays[lane * 3 + 2] = r2;
-    sx.keys[lane] = ~0ull; sx.occl[lane] = 0u;
+    sx.keys[lane] = ~0ull; sx.occl[lane] = 0;
     for (;;) {
         // ---- pool the candidates of all lanes: round j takes every lane's j-th candidate (shadow ray first)
         uint32_t n_items = 0;
         for (;;) {
             const bool has = (ms | me) != 0u;
             const unsigned long long b = __ballot(has);
-            if (b == 0ull || n_items + 64u > kItemCap) break;
+            if (b == 0ull || n_items + 64u > sx.item_cap) break;
             if (has) {
                 uint32_t leaf, kind;
                 if (ms) { leaf = (uint32_t)(sx.n_used - 1) - (uint32_t)__builtin_ctz(ms); ms &= ms - 1u; kind = 1u; }
@@ -173,7 +185,7 @@ __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool h
                         t = (float)td;
                     }
                     if (hit) {
-                        if (kind) sx.occl[src] = 1u;
+                        if (kind) sx.occl[src] = 1;
                         else (void)__hip_atomic_fetch_min(&sx.keys[src], ((unsigned long long)f2u(t) << 32) | (unsigned long long)(((uint32_t)gprim << 16) | (uint32_t)pi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                     }
                 }
@@ -223,7 +235,14 @@ __device__ __forceinline__ void opaque_state(PathState &ps) {
     opaque(ps.W); opaque(ps.rr); opaque(ps.p2); opaque(ps.rad); opaque(ps.nee); opaque(ps.eta_scale); opaque(ps.spread);
 }
 
+// A dead lane starts the path of stash slot `slot` (generated by whichever lane had that index; same values as generate_path on this lane)
+__device__ __forceinline__ void stash_start(const DScene &sc, const ScanCtx &sx, uint32_t st_base, uint32_t slot, PathState &ps) {
+    const f3 dir = mk3(sx.st_dir[slot], sx.st_dir[64 + slot], sx.st_dir[128 + slot]);
+    start_path(sc, st_base + slot, dir, sx.st_rng[slot], ps);
+}
+
 // LDS image of the scan area at byte offset `at` (16-byte aligned): [leaf table][primitives, transposed][4 x wave scratch]
+template <uint32_t ITEM_CAP, bool STASH>
 __device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at) {
     ScanCtx sx;
     char *base = (char *)lj_smem + at;
@@ -233,17 +252,19 @@ __device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at) {
     LJ_LDS v4f *lp = (LJ_LDS v4f *)(base + lt_bytes);
     const v4f *src = reinterpret_cast<const v4f *>(sc.leaf_prims);
     for (int i = threadIdx.x; i < sc.n_prims * 3; i += kBlock) lp[(i % 3) * sc.n_prims + (i / 3)] = src[i];
-    char *wave = base + lt_bytes + (uint32_t)sc.n_prims * 48u + (threadIdx.x >> 6) * kWaveScanBytes;
+    char *wave = base + lt_bytes + (uint32_t)sc.n_prims * 48u + (threadIdx.x >> 6) * wave_scan_bytes(ITEM_CAP, STASH);
     sx.boxes = (const LJ_CONST float *)(uintptr_t)sc.scan_leaves; sx.n_used = sc.n_scan_used;
     sx.leaf_tab = lt; sx.lprims = lp; sx.prim_stride = sc.n_prims; sx.spheres = sc.spheres;
-    sx.rays = (LJ_LDS v4f *)wave; sx.keys = (LJ_LDS unsigned long long *)(wave + 64 * 48); sx.occl = (LJ_LDS uint32_t *)(wave + 64 * 48 + 64 * 8);
-    sx.items = (LJ_LDS uint16_t *)(wave + 64 * 48 + 64 * 8 + 64 * 4);
+    sx.rays = (LJ_LDS v4f *)wave; sx.keys = (LJ_LDS unsigned long long *)(wave + 64 * 48);
+    sx.st_rng = (LJ_LDS uint64_t *)(wave + 64 * 48 + 64 * 8); sx.st_dir = (LJ_LDS float *)(wave + 64 * 48 + 64 * 8 + kRegenSlots * 8);
+    const uint32_t after = 64 * 48 + 64 * 8 + (STASH ? kWaveStashBytes : 0u);   // (without a stash st_rng / st_dir are never used)
+    sx.occl = (LJ_LDS uint8_t *)(wave + after); sx.items = (LJ_LDS uint16_t *)(wave + after + 64); sx.item_cap = ITEM_CAP;
     return sx;
 }
-size_t scan_smem(int n_scan_leaves, int n_prims) { return (((size_t)n_scan_leaves * 8 + 15) & ~(size_t)15) + (size_t)n_prims * 48 + 4 * (size_t)kWaveScanBytes; }
+size_t scan_smem(int n_scan_leaves, int n_prims, uint32_t item_cap = kItemCap, bool stash = false) { return (((size_t)n_scan_leaves * 8 + 15) & ~(size_t)15) + (size_t)n_prims * 48 + 4 * (size_t)wave_scan_bytes(item_cap, stash); }
 
 // waves per SIMD the kernel is built for.  The Lambert-only instantiation needs 113 VGPRs unconstrained; built for five waves (96
-// VGPRs, 7 of them spilled to scratch) it is 7 % faster than for four — the kernel waits on LDS round trips and dependent issue,
+// VGPRs, 6 of them spilled to scratch) it is 7 % faster than for four — the kernel waits on LDS round trips and dependent issue,
 // which a fifth wave hides (measured on MI355X, cbox 256 spp: 3 waves 17.8 ms, 4: 16.1, 5: 14.9, 6: 15.7 with 43 spills).  The
 // feature sets with textures, microfacet lobes or sphere lights need ~150 VGPRs and spill 25-70 registers already at four: three.
 #ifndef LJ_MEGA_OCC
@@ -255,19 +276,31 @@ template <> struct MegaOccupancy<FeatLambert> { static constexpr int waves = LJ_
 #define LJ_MEGA_OCC_PLASTIC 4
 #endif
 template <> struct MegaOccupancy<FeatPlastic> { static constexpr int waves = LJ_MEGA_OCC_PLASTIC; };
+// Which builds generate camera samples 64 at a time into a per-wave stash (k_mega below).  It pays where paths are short: on cbox (4.02
+// steps per path, 29 % of lane slots idle) it takes 4.3 % off a render; on veach_mi (Plastic: 85 % of the lanes live anyway) it cost 0.9 %
+// (profiles/mega_stash_ab.txt).  So: the five-wave Lambert build only; every other build regenerates lane by lane, as before.
+#ifndef LJ_MEGA_STASH
+#define LJ_MEGA_STASH 1
+#endif
+template <class Ft> constexpr bool mega_stash() { return LJ_MEGA_STASH && MegaOccupancy<Ft>::waves >= 5; }
+#ifndef LJ_MEGA_ITEM_CAP_TIGHT   // (developer A/B: the small pool without the stash)
+#define LJ_MEGA_ITEM_CAP_TIGHT 0
+#endif
+template <class Ft> constexpr uint32_t mega_item_cap() { return (mega_stash<Ft>() || (LJ_MEGA_ITEM_CAP_TIGHT && MegaOccupancy<Ft>::waves >= 5)) ? kItemCapTight : kItemCap; }
 
 // stats: [0] bounce iterations, [1] closest-hit rays, [2] shadow rays, [3] samples finished, [4] path steps (shade_path calls)
 template <class Ft, bool SPHERES>
 __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScene sc, DPass pass, ShadeStage stg, uint32_t scan_at, uint32_t n_samples, uint32_t grab,
                                                               uint32_t *sample_counter, unsigned long long *stats) {
     stage_shade_tables<2>(sc, stg, 0u);
-    const ScanCtx sx = stage_scan(sc, scan_at);
+    constexpr bool STASH = mega_stash<Ft>();
+    const ScanCtx sx = stage_scan<mega_item_cap<Ft>(), STASH>(sc, scan_at);
     __syncthreads();
     const uint32_t lane = lane_id();
     ShadeCounters cnt; cnt.bounces = cnt.closest = cnt.shadow = cnt.done = 0;
     uint32_t steps = 0;
-    bool live = false, exhausted = false;
-    uint32_t w_next = 0, w_end = 0;   // the wave's open range of camera samples (wave-uniform)
+    bool live = false;
+    RegenState rg; regen_init(rg);   // wave-uniform: the wave's open range of camera samples and its stash (dregen.h)
     PathState ps;
     ps.flags = 0u; ps.stfar = 0.0f; ps.sample = 0u;
     for (;;) {
@@ -283,22 +316,59 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
         }
         // ---- lanes without a path take the next camera samples (path_tracing.h:10-14)
         const unsigned long long dead = __ballot(!live);
-        if (dead != 0ull && !exhausted) {
-            if (w_next == w_end) {
-                uint32_t b = 0;
-                if (lane == 0u) b = atomicAdd(sample_counter, grab);
-                b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
-                if (b >= n_samples) exhausted = true;
-                else { w_next = b; w_end = (n_samples - b < grab) ? n_samples : b + grab; }
+        if constexpr (STASH) {
+            // first what the wave's stash still holds; when that runs out the wave generates its next 64 samples with all lanes at once (a
+            // quarter of the lanes end per step: generated lane by lane, the block would be issued every step three quarters empty) and the
+            // lanes still waiting are served from the new fill
+            uint32_t n_dead = (uint32_t)__popcll(dead);
+            if (n_dead != 0u) {
+                uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+                uint32_t first;
+                uint32_t take = regen_take(rg, n_dead, first);
+                if (!live && rank < take) { stash_start(sc, sx, rg.st_base, first + rank, ps); live = true; }
+                n_dead -= take; rank -= take;   // (rank of a lane that is still dead among those still dead)
+                if (n_dead != 0u) {
+                    if (regen_needs_grab(rg)) {
+                        uint32_t b = 0;
+                        if (lane == 0u) b = atomicAdd(sample_counter, grab);
+                        regen_grabbed(rg, (uint32_t)__builtin_amdgcn_readfirstlane((int)b), n_samples, grab);
+                    }
+                    const uint32_t n_gen = regen_refill(rg);
+                    if (n_gen != 0u) {
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();   // the reads above come first
+                        if (lane < n_gen) {
+                            f3 dir; uint64_t rng;
+                            camera_sample(sc, pass, rg.st_base + lane, dir, rng);
+                            sx.st_rng[lane] = rng; sx.st_dir[lane] = dir.x; sx.st_dir[64 + lane] = dir.y; sx.st_dir[128 + lane] = dir.z;
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+                        take = regen_take(rg, n_dead, first);
+                        if (!live && rank < take) { stash_start(sc, sx, rg.st_base, first + rank, ps); live = true; }
+                    }
+                }
             }
-            if (!exhausted) {
-                const uint32_t left = w_end - w_next, n_dead = (uint32_t)__popcll(dead);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
-                if (!live && rank < left) { generate_path(sc, pass, w_next + rank, ps); live = true; }
-                w_next += n_dead < left ? n_dead : left;
+            // No lane is live here only if the wave may end.  Every lane was dead and asked for a sample, so regen_take drained the stash; lanes
+            // were left over, so the wave went to the counter unless its range was still open, and refilled unless the range was empty — and a
+            // refill of n >= 1 slots makes a lane live.  So: stash empty, range empty, counter exhausted, which is regen_done(rg); the host
+            // model (tests/twin_regen) asserts the implication on every iteration.  Written as this plain test the loop also keeps the
+            // shape the register allocator handles well (6 VGPRs spilled in the Lambert build, as without the stash).
+            if (__ballot(live) == 0ull) break;
+        } else {
+            if (dead != 0ull && !rg.exhausted) {   // lane by lane, straight off the wave's open range
+                if (rg.w_next == rg.w_end) {
+                    uint32_t b = 0;
+                    if (lane == 0u) b = atomicAdd(sample_counter, grab);
+                    regen_grabbed(rg, (uint32_t)__builtin_amdgcn_readfirstlane((int)b), n_samples, grab);
+                }
+                if (!rg.exhausted) {
+                    const uint32_t left = rg.w_end - rg.w_next, n_dead = (uint32_t)__popcll(dead);
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+                    if (!live && rank < left) { generate_path(sc, pass, rg.w_next + rank, ps); live = true; }
+                    rg.w_next += n_dead < left ? n_dead : left;
+                }
             }
+            if (__ballot(live) == 0ull) { if (rg.exhausted) break; else continue; }
         }
-        if (__ballot(live) == 0ull) { if (exhausted) break; else continue; }
         // ---- both rays of the vertex: the pending shadow ray [eps, (1 - eps) d] and the extension ray [eps, inf) (camera rays from 0)
         opaque_state(ps);
         const bool has_e = live && !(ps.flags & PF_NO_EXT), has_s = live && ps.stfar > 0.0f;
@@ -325,7 +395,7 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
 struct RayIO { float org[3]; float tnear; float dir[3]; float tfar; };
 struct HitIO { float t, u, v; int32_t shape_id, prim_id; };
 __global__ void __launch_bounds__(kBlock) k_trace_rays_scan(DScene sc, const RayIO *rays, long long n, HitIO *hits, unsigned char *occ) {
-    const ScanCtx sx = stage_scan(sc, 0u);
+    const ScanCtx sx = stage_scan<kItemCap, false>(sc, 0u);
     __syncthreads();
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long i0 = (long long)blockIdx.x * kBlock; i0 < n; i0 += stride) {   // wave-complete iterations
@@ -354,15 +424,20 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays_scan(DScene sc, const Ray
 // LDS a k_mega workgroup needs (0: the scene cannot run as a mega launch)
 size_t mega_smem(const DScene &sc, const ShadeConfig &scfg) {
     if (sc.n_scan_leaves <= 0 || !scfg.stage_prims || scfg.smem == 0) return 0;
-    const size_t at = (scfg.smem + 15) & ~(size_t)15, total = at + scan_smem(sc.n_scan_leaves, sc.n_prims);
+    uint32_t item_cap = kItemCap; bool stash = false;
+    with_shade_variant(scfg.variant, [&](auto ft) { item_cap = mega_item_cap<decltype(ft)>(); stash = mega_stash<decltype(ft)>(); });
+    const size_t at = (scfg.smem + 15) & ~(size_t)15, total = at + scan_smem(sc.n_scan_leaves, sc.n_prims, item_cap, stash);
     return total <= 64 * 1024 ? total : 0;
 }
 
-// workgroups per CU a mega launch keeps resident (the grid is persistent: n_cus * this)
-int mega_blocks_per_cu(const ShadeConfig &scfg) {
+// workgroups per CU a mega launch keeps resident (the grid is persistent: n_cus * this): what the registers allow, and no more than
+// fit the CU's 160 KiB of LDS
+int mega_blocks_per_cu(const DScene &sc, const ShadeConfig &scfg) {
     int waves = 3;
     with_shade_variant(scfg.variant, [&](auto ft) { waves = MegaOccupancy<decltype(ft)>::waves; });
-    return waves;
+    const size_t smem = (mega_smem(sc, scfg) + kLdsGranule - 1) / kLdsGranule * kLdsGranule;
+    const int by_lds = smem ? (int)(kLdsPerCU / smem) : waves;
+    return waves < by_lds ? waves : by_lds;
 }
 
 void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, bool spheres, uint32_t n_samples, uint32_t grab, uint32_t *sample_counter,
