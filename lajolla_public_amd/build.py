@@ -181,6 +181,23 @@ def build_twin_regen(verbose=True):
     return TWIN_REGEN_LIB
 
 
+TWIN_SCAN_LIB = os.path.join(ROOT, "tests", "twin_scan", "_build", "libljtwinscan_asan.so" if _SAN else "libljtwinscan.so")
+
+
+def build_twin_scan(verbose=True):
+    """Host build of the leaf scan's box arithmetic and table conversion (device/dscan.h) for the CPU-side tests."""
+    src = os.path.join(ROOT, "tests", "twin_scan", "twin_scan.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_SCAN_LIB), exist_ok=True)
+    if _stale(TWIN_SCAN_LIB, [src] + _headers()):
+        if verbose:
+            print("[build] compiling the host twin of the leaf scan's box test (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2", "-ffp-contract=off"] + _SAN_FLAGS + _host_fma_flag() + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+              "-o", TWIN_SCAN_LIB, src])
+    return TWIN_SCAN_LIB
+
+
 def build_reference_subset():
     """oracle/_ref from the reference's own sources — only where /root/reference exists (this container)."""
     script = os.path.join(ROOT, "oracle", "ref_build.sh")
@@ -196,4 +213,5 @@ if __name__ == "__main__":
         build_twin()
         build_twin_tile()
         build_twin_regen()
+        build_twin_scan()
     print(LIB)

@@ -685,6 +685,7 @@ static int trace_batch(lj_scene *scene, int64_t n, const LjRay *rays_host, LjHit
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
         scene->stats = LjStats{}; scene->stats.render_ms = ms; scene->stats.rays_closest = hits_host ? (uint64_t)n : 0; scene->stats.rays_shadow = hits_host ? 0 : (uint64_t)n;   // (the query kernel's device time)
+        if (scan) scene->stats.mega_launches = 1; else scene->stats.extend_launches = 1;   // which route answered: the leaf scan of mega.hip or the BVH traversal
     });
 }
 int lj_intersect(lj_scene *scene, int64_t n, const LjRay *rays_host, LjHit *hits_host) {

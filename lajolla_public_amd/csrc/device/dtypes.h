@@ -75,9 +75,10 @@ static_assert(sizeof(DPrimShade) == 112, "DPrimShade layout");
 
 struct DSphere { double center[3]; double radius; int32_t gprim, _pad; };   // gprim: the sphere's global primitive id
 
-// One leaf of a tiny scene's flat leaf table (dscan.h): padded box + its primitives [first, first + count) of the leaf-ordered
-// primitive array.  32 bytes: one s_load_dwordx8.
-struct DScanLeaf { float lo[3], hi[3]; int32_t first, count; };
+// One leaf of a tiny scene's flat leaf table (dscan.h): padded box, as centre c and half-extent h (the box test then needs no ordering of
+// plane pairs by the ray's direction signs; [c - h, c + h] contains the builder's padded box, scan_leaf_from_box) + its primitives
+// [first, first + count) of the leaf-ordered primitive array.  32 bytes: one s_load_dwordx8.
+struct DScanLeaf { float c[3], h[3]; int32_t first, count; };
 static_assert(sizeof(DScanLeaf) == 32, "DScanLeaf must be 32 bytes");
 
 struct DTexture {

@@ -19,6 +19,7 @@
 #include "dtrace.h"
 #include "dconfig.h"
 #include "dregen.h"
+#include "dscan.h"
 
 namespace ljd {
 
@@ -53,43 +54,22 @@ struct ScanCtx {
 
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
-// Leaf-box scan: one bit of a ray's mask per leaf box its segment [tnear, tfar] overlaps.  Same slab arithmetic as the BVH node step
-// (t = plane * (1/d) - o * (1/d), v_rcp reciprocals, exit widened by 4 ulp; the boxes carry the builder's 1e-5 padding), with
-// min / max instead of sign-selected planes because the planes are scalars here.  A direction component closer to zero than
-// 1e-18 is moved there: the slab then spans |t| < 1e18 * (distance to the plane) instead of producing inf - inf.  It can only
-// mis-decide a slab whose plane lies within float rounding of the ray's origin, and the padding keeps every primitive of the box
-// 100 times further inside than that.
-struct ScanRay { float ix, iy, iz, ox, oy, oz; };
+// Leaf-box scan: one bit of a ray's mask per leaf box its segment [tnear, tfar] overlaps.  Slab arithmetic on the table's centre /
+// half-extent records (dscan.h: scan_box with its error argument, the 1e-18 clamp of tiny direction components; exit widened by 4 ulp;
+// the boxes carry the builder's 1e-5 padding), 14 vector instructions per box for an extension ray and 15 for a shadow ray.  The
+// reciprocals are v_rcp_f32 as in the BVH node step.
 __device__ __forceinline__ ScanRay scan_ray(f3 org, f3 dir) {
-    const float tiny = 1e-18f;
-    const float dx = fabsf(dir.x) < tiny ? copysignf(tiny, dir.x) : dir.x, dy = fabsf(dir.y) < tiny ? copysignf(tiny, dir.y) : dir.y,
-                dz = fabsf(dir.z) < tiny ? copysignf(tiny, dir.z) : dir.z;
     ScanRay r;
-    r.ix = __builtin_amdgcn_rcpf(dx); r.iy = __builtin_amdgcn_rcpf(dy); r.iz = __builtin_amdgcn_rcpf(dz);
+    r.ix = __builtin_amdgcn_rcpf(scan_clamp_dir(dir.x)); r.iy = __builtin_amdgcn_rcpf(scan_clamp_dir(dir.y));
+    r.iz = __builtin_amdgcn_rcpf(scan_clamp_dir(dir.z));
     r.ox = org.x * r.ix; r.oy = org.y * r.iy; r.oz = org.z * r.iz;
     return r;
-}
-// One box against one ray; FAR: the segment has a far end (shadow rays; extension rays run to infinity).  Returns te - 1.0000005 tx in one
-// rounding: NEGATIVE (sign bit set) when the segment overlaps the box.  The scan shifts that sign bit into the ray's candidate mask with
-// one v_alignbit — no compare, no select.  (Against `te <= round(tx * 1.0000005)` the decision can differ only for |te - tx c| below one
-// rounding, i.e. for boxes the exact ray touches in a single point behind its own 4-ulp allowance; which boxes are entered never changes
-// a hit — the closest hit is the (t, primitive) minimum over every box that holds it — it only has to stay conservative.)
-// `tnear` must be a canonical number (the callers pass max(tnear, 0)), so that the maximum below compiles without a quieting copy.
-template <bool FAR>
-__device__ __forceinline__ float scan_box(const float (&b)[6], const ScanRay &r, float tnear, float tfar) {
-    const float ax = __builtin_fmaf(b[0], r.ix, -r.ox), bx = __builtin_fmaf(b[3], r.ix, -r.ox);
-    const float ay = __builtin_fmaf(b[1], r.iy, -r.oy), by = __builtin_fmaf(b[4], r.iy, -r.oy);
-    const float az = __builtin_fmaf(b[2], r.iz, -r.oz), bz = __builtin_fmaf(b[5], r.iz, -r.oz);
-    const float te = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tnear));
-    float tx = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-    if (FAR) tx = fminf(tx, tfar);
-    return __builtin_fmaf(tx, -1.0000005f, te);
 }
 __device__ __forceinline__ uint32_t shift_in_sign(uint32_t mask, float d) { return __builtin_amdgcn_alignbit(mask, f2u(d), 31u); }   // (mask << 1) | sign(d)
 
 // Both rays of a path (E: some lane has an extension ray, S: some lane has a shadow ray — wave-uniform, decided outside the loop) against
-// every leaf box in ONE pass over the table: the boxes are fetched (scalar loads, four boxes ahead) once, and the two independent slab
-// chains interleave.  Bit (n_used - 1 - k) of a ray's mask = its segment overlaps leaf box k (the bits are shifted in from below).
+// every leaf box in ONE pass over the table: the boxes (centre | half-extent) are fetched (scalar loads, four boxes ahead) once, and the two
+// independent slab chains interleave.  Bit (n_used - 1 - k) of a ray's mask = its segment overlaps leaf box k (the bits are shifted in from below).
 template <bool E, bool S>
 __device__ __forceinline__ void scan_leaf_boxes(const ScanCtx &sx, const ScanRay &re, float tnear_e, const ScanRay &rs, float tnear_s, float tfar_s, uint32_t &me, uint32_t &ms) {
     const int n = sx.n_used;

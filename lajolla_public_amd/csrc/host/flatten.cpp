@@ -1,6 +1,7 @@
 // Scene flattening: the host half of Scene::Scene (scene.cpp:3-53).  All derived quantities are computed in
 // double exactly as the reference computes them and narrowed to float once, at the end.
 #include "flatten.h"
+#include "../device/dscan.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -302,13 +303,14 @@ FlatScene flatten_scene(const LjSceneDesc &d) {
         for (const auto &nd : F.nodes) for (int k = 0; k < 4; k++) {
             if (nd.child[k] >= 0 || !(nd.lox[k] <= nd.hix[k])) continue;
             ljd::DScanLeaf L{};
-            L.lo[0] = nd.lox[k]; L.lo[1] = nd.loy[k]; L.lo[2] = nd.loz[k]; L.hi[0] = nd.hix[k]; L.hi[1] = nd.hiy[k]; L.hi[2] = nd.hiz[k];
+            const float blo[3] = {nd.lox[k], nd.loy[k], nd.loz[k]}, bhi[3] = {nd.hix[k], nd.hiy[k], nd.hiz[k]};
+            ljd::scan_leaf_from_box(blo, bhi, L.c, L.h);
             L.first = (~nd.child[k]) >> 3; L.count = ((~nd.child[k]) & 7) + 1;
             leaves.push_back(L);
         }
         if (leaves.size() <= 32 && F.leaf_prims.size() <= 256 && !leaves.empty()) {
             F.n_scan_used = (int)leaves.size();
-            while (leaves.size() % 4) { ljd::DScanLeaf L{}; for (int k = 0; k < 3; k++) L.lo[k] = L.hi[k] = 1e18f; L.first = 0; L.count = 0; leaves.push_back(L); }
+            while (leaves.size() % 4) { ljd::DScanLeaf L{}; for (int k = 0; k < 3; k++) { L.c[k] = 1e18f; L.h[k] = 0.0f; } L.first = 0; L.count = 0; leaves.push_back(L); }
             F.scan_leaves = leaves;
         }
     }
