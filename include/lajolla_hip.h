@@ -228,6 +228,33 @@ int lj_render(lj_scene *scene, const LjRenderArgs *args, float *rgb_host);
  * hand-off used for the RCCL framebuffer reduce. */
 int lj_render_device(lj_scene *scene, const LjRenderArgs *args, float *rgb_device, void *hip_stream);
 
+/* ---- cameras of an uploaded scene
+ * Everything lj_scene_upload spends time on (the BVH, the light, environment-map and texture tables) is independent of the camera;
+ * these calls move the camera of a scene that is already on the device.
+ *
+ * lj_camera_look_at: Camera::Camera (camera.cpp:7-21) behind look_at (transform.cpp), exactly as the XML front end builds the camera of a
+ * <lookat> sensor: host only.  fov: degrees, the value Camera::Camera takes (the "x" axis fov, i.e. after parse_sensor's fovAxis
+ * conversion).  medium_id = -1. */
+int lj_camera_look_at(const double origin[3], const double target[3], const double up[3], double fov,
+                      int32_t width, int32_t height, int32_t filter_kind, double filter_param, LjCamera *out);
+
+/* Replace the camera of an uploaded scene.  Everything lj_scene_upload derives from the camera is re-derived by the same code; nothing
+ * else is rebuilt.  Film size and filter may change.  Later lj_render* / lj_*_queries calls see the new camera. */
+int lj_scene_set_camera(lj_scene *scene, const LjCamera *camera);
+
+/* n_views renders of the scene in one pass: rgb[n_views][h][w][3].  Every view must have the scene camera's width, height, filter_kind,
+ * filter_param and medium_id (else LJ_ERR_INVALID_ARG); cam_to_world and sample_to_cam are per view.  View v is bit-identical to
+ * lj_render of the same scene uploaded with views[v] and the same args: the batch is rendered as one frame of n_views * h rows whose
+ * pcg32 streams are those of the pixel inside its view, (y*w + x)*spp + s.
+ * args: spp, max_depth, seed, pool_paths and flags as for lj_render; rank / world_size and the crop window apply to every view (pixels
+ * outside the share or window are 0, so the sum over ranks of a batch is the full batch); rng_mode must be LJ_RNG_SAMPLE (LJ_RNG_TILE:
+ * LJ_ERR_UNSUPPORTED).  All integrators.  LJ_ERR_INVALID_ARG: n_views <= 0, NULL pointers, a matrix that is not finite,
+ * n_views * w * h > 2^31.  lj_get_stats afterwards reports the sums over all views.  (Device groups have no batched call.) */
+int lj_render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_host);
+/* Same, into caller-owned DEVICE memory; ordering on `hip_stream` as lj_render_device. */
+int lj_render_views_device(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views,
+                           float *rgb_device, void *hip_stream);
+
 /* Per-sample radiance for the crop window: out[((y-y0)*(x1-x0) + (x-x0))*spp + s][3] — one path_tracing()
  * value (path_tracing.h:7-325) per entry, for path-by-path parity tests. */
 int lj_render_samples(lj_scene *scene, const LjRenderArgs *args, float *radiance_host);

@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 from . import _abi
-from ._abi import LjRenderArgs, LjSceneDesc, LjStats, LjSceneInfo, LjRay, LjHit
+from ._abi import LjRenderArgs, LjSceneDesc, LjStats, LjSceneInfo, LjRay, LjHit, LjCamera
 from ._abi import LJ_RNG_SAMPLE, LJ_RNG_TILE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -174,6 +174,15 @@ class Scene:
         _check(load_library().lj_get_stats(self._h, C.byref(st)))
         return st
 
+    def set_camera(self, cam):
+        """Replace the scene's camera (an LjCamera, e.g. from look_at_camera) without rebuilding anything else; film size and
+        filter may change.  Later renders and queries see the new camera."""
+        lib = load_library()
+        _check(lib.lj_scene_set_camera(self._h, C.byref(cam)))
+        info = LjSceneInfo()
+        _check(lib.lj_scene_info(self._h, C.byref(info)))
+        self.info = info
+
 
 def make_args(spp=0, max_depth=None, rank=0, world_size=1, crop=None, pool_paths=0, seed=0, flags=0, rng_mode=_abi.LJ_RNG_SAMPLE):
     """rng_mode: _abi.LJ_RNG_SAMPLE (one pcg32 stream per pixel sample, the default) or _abi.LJ_RNG_TILE (the reference's render()
@@ -203,6 +212,40 @@ def render_device(scene, device_ptr, stream=None, **kw):
     """Same, into caller-owned device memory (e.g. a torch tensor's data_ptr()) on a HIP stream; asynchronous."""
     args = make_args(**kw)
     _check(load_library().lj_render_device(scene._h, C.byref(args), C.c_void_p(int(device_ptr)), C.c_void_p(int(stream or 0))))
+
+
+def look_at_camera(origin, target, up, fov, width, height, filter_kind=_abi.LJ_FILTER_BOX, filter_param=1.0, medium_id=-1):
+    """The LjCamera the XML front end builds for a perspective sensor with a <lookat> transform: fov in degrees along x."""
+    d3 = C.c_double * 3
+    cam = LjCamera()
+    _check(load_library().lj_camera_look_at(d3(*[float(v) for v in origin]), d3(*[float(v) for v in target]), d3(*[float(v) for v in up]),
+                                            float(fov), int(width), int(height), int(filter_kind), float(filter_param), C.byref(cam)))
+    cam.medium_id = int(medium_id)
+    return cam
+
+
+def _camera_array(cameras):
+    arr = (LjCamera * len(cameras))()
+    for i, c in enumerate(cameras):
+        C.memmove(C.addressof(arr[i]), C.addressof(c), C.sizeof(LjCamera))
+    return arr
+
+
+def render_views(scene, cameras, **kw):
+    """Many cameras of one uploaded scene in one pass: (n, h, w, 3) float32.  `cameras`: a sequence of LjCamera with the scene camera's film,
+    filter and medium.  View v is bit-identical to render() of the scene uploaded with cameras[v] and the same arguments."""
+    args = make_args(**kw)
+    cams = _camera_array(cameras)
+    out = np.empty((len(cameras), scene.info.height, scene.info.width, 3), np.float32)
+    _check(load_library().lj_render_views(scene._h, C.byref(args), len(cameras), cams, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def render_views_device(scene, cameras, device_ptr, stream=None, **kw):
+    """Same, into caller-owned device memory of n * h * w * 3 floats (e.g. a torch tensor's data_ptr()), ordered on a HIP stream as render_device."""
+    args = make_args(**kw)
+    cams = _camera_array(cameras)
+    _check(load_library().lj_render_views_device(scene._h, C.byref(args), len(cameras), cams, C.c_void_p(int(device_ptr)), C.c_void_p(int(stream or 0))))
 
 
 def render_samples(scene, crop, **kw):

@@ -11,7 +11,8 @@ LJ_TEX_CONSTANT, LJ_TEX_IMAGE, LJ_TEX_CHECKERBOARD = 0, 1, 2
 LJ_LIGHT_AREA, LJ_LIGHT_ENVMAP = 0, 1
 MATERIAL_KINDS = ["lambertian", "roughplastic", "roughdielectric", "disneydiffuse", "disneymetal",
                   "disneyglass", "disneyclearcoat", "disneysheen", "disneybsdf"]
-LJ_INTEGRATOR_PATH = 5
+LJ_INTEGRATOR_DEPTH, LJ_INTEGRATOR_SHADING_NORMAL, LJ_INTEGRATOR_MEAN_CURVATURE, LJ_INTEGRATOR_RAY_DIFFERENTIAL, LJ_INTEGRATOR_MIPMAP_LEVEL = 0, 1, 2, 3, 4
+LJ_INTEGRATOR_PATH, LJ_INTEGRATOR_VOLPATH = 5, 6
 LJ_MAX_TEX_SLOTS = 12
 INT32_MIN = -2**31
 
@@ -204,6 +205,11 @@ SYMBOLS = [
     ("lj_render", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_void_p]),
     ("lj_render_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_void_p, C.c_void_p]),
     ("lj_render_samples", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_void_p]),
+    ("lj_camera_look_at", C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(LjCamera)]),
+    ("lj_scene_set_camera", C.c_int, [C.c_void_p, C.POINTER(LjCamera)]),
+    ("lj_render_views", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p]),
+    ("lj_render_views_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p, C.c_void_p]),
     ("lj_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_occluded", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_get_stats", C.c_int, [C.c_void_p, C.POINTER(LjStats)]),

@@ -198,6 +198,24 @@ def build_twin_scan(verbose=True):
     return TWIN_SCAN_LIB
 
 
+TWIN_VIEWS_LIB = os.path.join(ROOT, "tests", "twin_views", "_build", "libljtwinviews_asan.so" if _SAN else "libljtwinviews.so")
+
+
+def build_twin_views(verbose=True):
+    """Host build of the camera-batch path of the device headers (DPass::views: lj_render_views) for the CPU-side tests; the flags of build_twin."""
+    src = os.path.join(ROOT, "tests", "twin_views", "twin_views.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_VIEWS_LIB), exist_ok=True)
+    deps = [src] + _headers() + [os.path.join(CSRC, s) for s in ("host/flatten.cpp", "host/bvh.cpp")]
+    if _stale(TWIN_VIEWS_LIB, deps):
+        if verbose:
+            print("[build] compiling the host twin of the camera-batch path (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2", "-ffp-contract=off"] + _SAN_FLAGS + _host_fma_flag() + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+              "-o", TWIN_VIEWS_LIB, src, os.path.join(CSRC, "host/flatten.cpp"), os.path.join(CSRC, "host/bvh.cpp"), "-lpthread"])
+    return TWIN_VIEWS_LIB
+
+
 def build_reference_subset():
     """oracle/_ref from the reference's own sources — only where /root/reference exists (this container)."""
     script = os.path.join(ROOT, "oracle", "ref_build.sh")
@@ -214,4 +232,5 @@ if __name__ == "__main__":
         build_twin_tile()
         build_twin_regen()
         build_twin_scan()
+        build_twin_views()
     print(LIB)

@@ -41,6 +41,9 @@ struct RenderPlan {
     int max_depth;
     int rng_mode;                                          // LJ_RNG_SAMPLE / LJ_RNG_TILE
     int rank, world, cx0, cy0, cx1, cy1;                   // the share and the crop window (the full frame when there is none)
+    // a batch of cameras (lj_render_views): `pixels` lists e = v*w*h + y*w + x — the single-view list, in its order, once per view — and
+    // views_dev is the batch's camera table on the device (0 / null: the scene's one camera)
+    int n_views = 0; const ljd::DCamera *views_dev = nullptr;
 };
 
 RenderPlan make_plan(const lj_scene *sc, const LjRenderArgs *a) {
@@ -87,6 +90,26 @@ RenderPlan make_plan(const lj_scene *sc, const LjRenderArgs *a) {
     }
     p.pixels = pixels; p.pixels_key = key;
     msc->plan_pixels = pixels; msc->plan_pixels_key = key;
+    return p;
+}
+
+// The plan of a batch of n_views cameras: the single-view plan of the same args (share and crop apply to every view) with its pixel list
+// repeated per view, offset by the view's first pixel in the n_views * h rows tall frame.
+RenderPlan make_views_plan(lj_scene *sc, const LjRenderArgs *a, int n_views) {
+    RenderPlan p = make_plan(sc, a);
+    if (p.rng_mode != LJ_RNG_SAMPLE) throw LjError(LJ_ERR_UNSUPPORTED, "lj_render_views: rng_mode must be LJ_RNG_SAMPLE (no per-tile schedule for a batch of cameras)");
+    const uint64_t view_pixels = (uint64_t)sc->flat.cam.width * (uint64_t)sc->flat.cam.height;
+    uint64_t key = (p.pixels_key ^ (0x9e3779b97f4a7c15ull + (uint64_t)n_views)) * 1099511628211ull; key |= 1ull;
+    p.n_views = n_views;
+    if (sc->views_pixels && sc->views_pixels_key == key) { p.pixels = sc->views_pixels; p.pixels_key = key; return p; }
+    auto all = std::make_shared<std::vector<uint32_t>>();
+    all->reserve(p.pixels->size() * (size_t)n_views);
+    for (int v = 0; v < n_views; v++) {
+        const uint32_t first = (uint32_t)((uint64_t)v * view_pixels);   // (n_views * w * h <= 2^31: checked by the caller)
+        for (uint32_t e : *p.pixels) all->push_back(first + e);
+    }
+    p.pixels = all; p.pixels_key = key;
+    sc->views_pixels = all; sc->views_pixels_key = key;
     return p;
 }
 
@@ -172,12 +195,19 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
     const uint64_t n_pix = plan.pixels->size();
     LjStats &st = sc->stats; st = LjStats{};
     if (n_pix == 0) return;
+    auto make_pass = [&](uint64_t p0, uint64_t np) {   // pixels [p0, p0 + np) of the list
+        ljd::DPass pass{};
+        pass.pixel_list = (const uint32_t *)ctx->pixel_list.p + p0; pass.n_pixels = (uint32_t)np; ljd::set_pass_divisors(pass, (uint32_t)plan.spp, (uint32_t)sc->flat.cam.width);
+        pass.seed = plan.seed; pass.sample_rgb = (float *)ctx->sample_rgb.p;
+        if (plan.n_views > 0) ljd::set_pass_views(pass, plan.views_dev, (uint32_t)sc->flat.cam.width, (uint32_t)sc->flat.cam.height);
+        return pass;
+    };
     if (sc->flat.integrator < LJ_INTEGRATOR_PATH) {   // auxiliary buffers: one primary ray per pixel, no queue
         if (samples_host) throw LjError(LJ_ERR_UNSUPPORTED, "the auxiliary integrators have one deterministic value per pixel, no per-sample values");
         upload_pixel_list(ctx, plan, stream);
         HIP_CHECK(hipEventRecord(ctx->ev_begin, stream));
         const int grid = (int)std::min<uint64_t>((n_pix + 255) / 256, (uint64_t)ctx->n_cus * 4);
-        ljd::launch_aux(sc->dscene, (const uint32_t *)ctx->pixel_list.p, (uint32_t)n_pix, sc->flat.integrator, rgb_dev, sc->ecfg,
+        ljd::launch_aux(sc->dscene, make_pass(0, n_pix), (uint32_t)n_pix, sc->flat.integrator, rgb_dev, sc->ecfg,
                         ensure_spill(ctx, sc->ecfg.spill_levels, (uint32_t)grid), grid, stream);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(ctx->ev_end, stream));
@@ -188,7 +218,9 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
     }
     if (plan.rng_mode == LJ_RNG_TILE) { run_tiles(sc, plan, ds, rgb_dev, samples_host, stream); return; }   // (the auxiliary integrators draw nothing: as above)
     // pass size: keep the per-sample radiance buffer <= ~1.5 GiB and sample ids in 32 bits
-    const uint64_t max_samples_pass = (uint64_t)1 << 27;
+    uint64_t max_samples_pass = (uint64_t)1 << 27;
+    // (developer knob: small passes, so that a test can put a pass boundary anywhere — inside a view of a batch, say — at a small size)
+    if (const char *e = getenv("LJ_TUNE_PASS_SAMPLES")) max_samples_pass = std::min<uint64_t>(max_samples_pass, (uint64_t)std::max(64ll, atoll(e)));
     uint64_t pix_per_pass = std::max<uint64_t>(1, max_samples_pass / (uint64_t)plan.spp);
     pix_per_pass = std::min<uint64_t>(pix_per_pass, n_pix);
     if (sc->flat.integrator == LJ_INTEGRATOR_VOLPATH) {   // volumetric path tracer: one lane per sample, whole path (dvol.h)
@@ -201,9 +233,7 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
         for (uint64_t p0 = 0; p0 < n_pix; p0 += pix_per_pass) {
             const uint64_t np = std::min<uint64_t>(pix_per_pass, n_pix - p0);
             const uint64_t total = np * (uint64_t)plan.spp;
-            ljd::DPass pass{};
-            pass.pixel_list = (const uint32_t *)ctx->pixel_list.p + p0; pass.n_pixels = (uint32_t)np; ljd::set_pass_divisors(pass, (uint32_t)plan.spp, (uint32_t)sc->flat.cam.width);
-            pass.seed = plan.seed; pass.sample_rgb = (float *)ctx->sample_rgb.p;
+            const ljd::DPass pass = make_pass(p0, np);
             // persistent grid (k_volpath regenerates paths): as many workgroups as stay resident, fewer for a small pass
             const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((total + 255) / 256, (uint64_t)ctx->n_cus * (uint64_t)ljd::volpath_blocks_per_cu(ds)));
             HIP_CHECK(hipMemsetAsync((char *)ctx->chunk_counter.p + 8, 0, 4, stream));   // the launch's sample counter
@@ -255,9 +285,7 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
         for (uint64_t p0 = 0; p0 < n_pix; p0 += pix_per_pass) {
             const uint64_t np = std::min<uint64_t>(pix_per_pass, n_pix - p0);
             const uint64_t total = np * (uint64_t)plan.spp;
-            ljd::DPass pass{};
-            pass.pixel_list = (const uint32_t *)ctx->pixel_list.p + p0; pass.n_pixels = (uint32_t)np; ljd::set_pass_divisors(pass, (uint32_t)plan.spp, (uint32_t)sc->flat.cam.width);
-            pass.seed = plan.seed; pass.sample_rgb = (float *)ctx->sample_rgb.p;
+            const ljd::DPass pass = make_pass(p0, np);
             HIP_CHECK(hipMemsetAsync(ctx->mega_state.p, 0, 64, stream));
             uint32_t grab = grab_max;
             if (!grab_fixed) {
@@ -384,9 +412,7 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
     for (uint64_t p0 = 0; p0 < n_pix; p0 += pix_per_pass) {
         const uint64_t np = std::min<uint64_t>(pix_per_pass, n_pix - p0);
         const uint64_t total = np * (uint64_t)plan.spp;
-        ljd::DPass pass{};
-        pass.pixel_list = (const uint32_t *)ctx->pixel_list.p + p0; pass.n_pixels = (uint32_t)np; ljd::set_pass_divisors(pass, (uint32_t)plan.spp, (uint32_t)sc->flat.cam.width);
-        pass.seed = plan.seed; pass.sample_rgb = (float *)ctx->sample_rgb.p;
+        const ljd::DPass pass = make_pass(p0, np);
         // contiguous sample ranges per workgroup, multiples of 64 so that a wave's first samples share a pixel
         {
             uint64_t per = ((total + n_blocks - 1) / n_blocks + 63) & ~(uint64_t)63;
@@ -648,6 +674,61 @@ int lj_render(lj_scene *scene, const LjRenderArgs *args, float *rgb_host) {
         HIP_CHECK(hipMemcpyAsync(rgb_host, ctx->frame.p, fb, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     });
+}
+
+int lj_scene_set_camera(lj_scene *scene, const LjCamera *camera) {
+    return lj::guard([&]() {
+        if (!scene || !camera) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_set_camera: null argument");
+        lj::check_camera(*camera);
+        lj::FlatScene &F = scene->flat;
+        if (camera->medium_id < -1 || camera->medium_id >= (int)F.media.size()) throw LjError(LJ_ERR_INVALID_ARG, "camera references a missing medium");
+        const bool resized = camera->width != F.cam.width || camera->height != F.cam.height;
+        F.cam = lj::flatten_camera(*camera); F.cam_medium = camera->medium_id;
+        // what a DScene holds of the camera, from the code that fills it at upload
+        const ljd::DScene h = F.host_view();
+        scene->dscene.cam = h.cam; scene->dscene.init_spread = h.init_spread; scene->dscene.cam_medium = h.cam_medium;
+        if (resized) { scene->plan_pixels.reset(); scene->plan_pixels_key = 0; scene->views_pixels.reset(); scene->views_pixels_key = 0; }   // lists of the old film
+    });
+}
+
+static void render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_host, float *rgb_device, hipStream_t caller, const char *who) {
+    if (!scene || !views || (!rgb_host && !rgb_device)) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    if (n_views <= 0) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": n_views must be positive");
+    const lj::FlatScene &F = scene->flat;
+    const uint64_t view_pixels = (uint64_t)F.cam.width * (uint64_t)F.cam.height;
+    if ((uint64_t)n_views * view_pixels > (1ull << 31)) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": more than 2^31 pixels in the batch");
+    std::vector<ljd::DCamera> table((size_t)n_views);
+    for (int v = 0; v < n_views; v++) {
+        lj::check_camera(views[v]);
+        table[v] = lj::flatten_camera(views[v]);
+        if (table[v].width != F.cam.width || table[v].height != F.cam.height || table[v].filter_kind != F.cam.filter_kind || table[v].filter_param != F.cam.filter_param ||
+            views[v].medium_id != F.cam_medium)
+            throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(v) + " differs from the scene camera in film size, filter or medium");
+    }
+    lj_context *ctx = scene->ctx;
+    set_device(ctx);
+    RenderPlan plan = make_views_plan(scene, args, n_views);
+    hipStream_t s = ctx->stream;
+    if (caller) { HIP_CHECK(hipEventRecord(ctx->ev_caller, caller)); HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_caller, 0)); }   // (as lj_render_device)
+    const size_t table_bytes = table.size() * sizeof(ljd::DCamera);
+    if (ctx->view_table.bytes < table_bytes) ctx->view_table.alloc(table_bytes);
+    HIP_CHECK(hipMemcpyAsync(ctx->view_table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
+    plan.views_dev = (const ljd::DCamera *)ctx->view_table.p;
+    const size_t fb = (size_t)n_views * view_pixels * 3 * sizeof(float);
+    float *frame = rgb_device;
+    if (!frame) { if (ctx->frame.bytes < fb) ctx->frame.alloc(fb); frame = (float *)ctx->frame.p; }
+    HIP_CHECK(hipMemsetAsync(frame, 0, fb, s));
+    run_render(scene, plan, frame, nullptr, s, args && (args->flags & 1u));
+    if (rgb_host) { HIP_CHECK(hipMemcpyAsync(rgb_host, frame, fb, hipMemcpyDeviceToHost, s)); HIP_CHECK(hipStreamSynchronize(s)); }
+    if (caller) { HIP_CHECK(hipEventRecord(ctx->ev_caller, s)); HIP_CHECK(hipStreamWaitEvent(caller, ctx->ev_caller, 0)); }
+}
+
+int lj_render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_host) {
+    return lj::guard([&]() { render_views(scene, args, n_views, views, rgb_host, nullptr, nullptr, "lj_render_views"); });
+}
+
+int lj_render_views_device(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_device, void *hip_stream) {
+    return lj::guard([&]() { render_views(scene, args, n_views, views, nullptr, rgb_device, (hipStream_t)hip_stream, "lj_render_views_device"); });
 }
 
 int lj_render_samples(lj_scene *scene, const LjRenderArgs *args, float *radiance_host) {

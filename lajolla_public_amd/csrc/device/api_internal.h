@@ -25,7 +25,7 @@ void launch_shade(const DScene &sc, const DPass &pass, const DQueue &q, const DQ
 void launch_resolve(const DPass &pass, uint32_t n_pixels, float *rgb, hipStream_t s);
 size_t tail_smem(const ExtendConfig &ecfg, const ShadeConfig &scfg);
 void launch_tail(const DScene &sc, const DPass &pass, const DQueue &q, DBlockState *blocks, uint32_t n_blocks, uint32_t seg, const ExtendConfig &ecfg, const ShadeConfig &scfg, int *spill, hipStream_t s);
-void launch_aux(const DScene &sc, const uint32_t *pixel_list, uint32_t n_pixels, int integrator, float *rgb, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
+void launch_aux(const DScene &sc, const DPass &pass, uint32_t n_pixels, int integrator, float *rgb, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
 void launch_volpath(const DScene &sc, const DPass &pass, uint32_t n_samples, uint32_t *counters, const ExtendConfig &cfg, int shade_variant, bool plain, int *spill, int grid, hipStream_t s);
 int volpath_blocks_per_cu(const DScene &sc);
 void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
@@ -81,6 +81,7 @@ struct lj_context {
     DevBuf blocks, sample_rgb, pixel_list, frame;
     uint64_t pixel_list_key = 0;   // which pixel list `pixel_list` holds (RenderPlan::pixels_key), 0: none
     DevBuf tile_cursors, tile_list, tile_samples;   // the per-tile schedule: one cursor per tile (dtile.h), the tile ids, per-sample radiance
+    DevBuf view_table;   // the camera table of a batch (lj_render_views): one DCamera per view, uploaded per call
     DevBuf mega_state;   // k_mega: [0] the grid-wide camera-sample counter (uint32), [8..] five 64-bit statistics
     ljd::DBlockState *blocks_host = nullptr;  // pinned, kMaxBlocks entries
     unsigned long long *stats_host = nullptr; // pinned, 8 entries: where a launch's statistics are read back (one wait per pass, no staged copy)
@@ -97,6 +98,7 @@ struct lj_scene {
     ljd::ShadeConfig scfg{};
     uint32_t feat_kinds = 0; bool feat_textured = false, feat_envmap = false, feat_sphere_lights = false;   // what the scene holds (picks scfg.variant)
     std::shared_ptr<const std::vector<uint32_t>> plan_pixels; uint64_t plan_pixels_key = 0;   // the last render plan's pixel list (make_plan)
+    std::shared_ptr<const std::vector<uint32_t>> views_pixels; uint64_t views_pixels_key = 0;   // ... and the last batch plan's (make_views_plan)
     std::vector<int64_t> shape_first_gprim;   // global primitive id of each shape's first primitive (shape order, then triangle order)
     LjStats stats{};
 };

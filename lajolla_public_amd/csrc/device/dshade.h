@@ -829,25 +829,72 @@ struct PathState {
 
 struct ShadeCounters { uint32_t bounces, closest, shadow, done; };
 
+// ---- a batch of cameras (DPass::views, lj_render_views): the frame is n_views x h rows tall, a pixel-list entry is e = v*w*h + y*w + x.
+// The pcg32 stream of a sample is that of the pixel INSIDE its view, (y*w + x)*spp + s: view v of a batch is then, bit for bit, the
+// render of a scene whose one camera is views[v].
+struct ViewPixel { uint32_t view, pixel; int x, y; };   // pixel = y*w + x
+LJ_HD ViewPixel view_decode(const DPass &pass, uint32_t e) {
+    ViewPixel r;
+    const uint32_t row = fast_div(e, pass.by_width);
+    r.x = (int)(e - row * pass.by_width.d);
+    r.view = fast_div(row, pass.by_height);
+    r.y = (int)(row - r.view * pass.by_height.d);
+    r.pixel = e - r.view * pass.view_pixels;
+    return r;
+}
+// f(camera of view `view`).  A wave's lanes mostly share a view (views change every w*h*spp samples): then the table entry is read with
+// scalar loads from the first lane's index — proven uniform by the ballot, not assumed — and only a wave that straddles a view
+// boundary gathers lane by lane.
+#ifndef LJ_CONST
+#define LJ_CONST __attribute__((address_space(4)))
+#endif
+template <class F>
+LJ_HD auto with_view_camera(const DPass &pass, uint32_t view, F &&f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)view);
+    if (__ballot(view != first) == 0ull) {
+        const LJ_CONST uint32_t *src = (const LJ_CONST uint32_t *)(uintptr_t)(pass.views + first);
+        DCamera cam;
+        static_assert(sizeof(DCamera) % 4 == 0, "DCamera is copied word by word");
+        uint32_t *dst = reinterpret_cast<uint32_t *>(&cam);
+#pragma unroll
+        for (uint32_t i = 0; i < sizeof(DCamera) / 4; i++) dst[i] = src[i];
+        return f(cam);
+    }
+#endif
+    return f(pass.views[view]);
+}
+
 // Camera-sample generation: path_tracing.h:10-14 + render.cpp:82 (per-sample stream variant).
 // In two pieces so that k_mega can compute samples with all lanes of a wave and start them on other lanes later (mega.hip):
 // camera_sample — everything that depends on the sample id: the primary direction and the pcg32 state after the two jitter draws;
+// VIEWS (here and below): the pass is a batch of cameras (DPass::views).  A compile-time switch, so that the kernels of a single camera
+// are the code they were: a test of the table pointer at run time costs the register-tuned instantiations registers (k_mega's
+// Lambert build: 6 -> 7 spilled VGPRs).
+template <bool VIEWS = false>
 LJ_HD void camera_sample(const DScene &sc, const DPass &pass, uint32_t sample_id, f3 &dir, uint64_t &rng) {
     const uint32_t p = fast_div(sample_id, pass.by_spp), s = sample_id - p * pass.spp;
-    const uint32_t pixel = pass.pixel_list[p];
-    const int y = (int)fast_div(pixel, pass.by_width), x = (int)(pixel - (uint32_t)y * (uint32_t)sc.cam.width);
+    uint32_t pixel = pass.pixel_list[p];
+    int x, y; uint32_t view = 0;
+    if constexpr (VIEWS) { const ViewPixel vp = view_decode(pass, pixel); view = vp.view; pixel = vp.pixel; x = vp.x; y = vp.y; }
+    else { y = (int)fast_div(pixel, pass.by_width); x = (int)(pixel - (uint32_t)y * (uint32_t)sc.cam.width); }
     const uint64_t stream = (uint64_t)pixel * pass.spp + s;
     const uint64_t inc = pcg32_inc(stream);
     uint64_t st = pcg32_init(stream, pass.seed);
     // the reference's g++ build gives the first draw to the y jitter and the second to x
     const float jy = pcg32_real(st, inc);
     const float jx = pcg32_real(st, inc);
-    dir = camera_primary_dir(sc.cam, x, y, jx, jy);
+    if constexpr (VIEWS) dir = with_view_camera(pass, view, [&](const DCamera &cam) { return camera_primary_dir(cam, x, y, jx, jy); });
+    else { (void)view; dir = camera_primary_dir(sc.cam, x, y, jx, jy); }
     rng = st;
 }
 // start_path — the path record of that sample: the two values above and constants.
-LJ_HD void start_path(const DScene &sc, uint32_t sample_id, f3 dir, uint64_t rng, PathState &ps) {
-    ps.org = ld3(sc.cam.org);
+template <bool VIEWS = false>
+LJ_HD void start_path(const DScene &sc, const DPass &pass, uint32_t sample_id, f3 dir, uint64_t rng, PathState &ps) {
+    if constexpr (VIEWS) {   // the sample's view, again from its id: nothing but the direction and the generator travels from camera_sample
+        const uint32_t view = view_decode(pass, pass.pixel_list[fast_div(sample_id, pass.by_spp)]).view;
+        ps.org = with_view_camera(pass, view, [&](const DCamera &cam) { return ld3(cam.org); });
+    } else ps.org = ld3(sc.cam.org);
     ps.dir = dir;
     ps.sdir = mk3(0, 0, 0); ps.stfar = 0.0f;
     ps.W = mk3(1, 1, 1); ps.rr = 1.0f; ps.p2 = -1.0f;
@@ -856,10 +903,11 @@ LJ_HD void start_path(const DScene &sc, uint32_t sample_id, f3 dir, uint64_t rng
     ps.eta_scale = 1.0f; ps.spread = sc.init_spread;
     ps.flags = 2u;  // num_vertices so far (camera + the vertex this ray will find); the first loop iteration is 3
 }
+template <bool VIEWS = false>
 LJ_HD void generate_path(const DScene &sc, const DPass &pass, uint32_t sample_id, PathState &ps) {
     f3 dir; uint64_t rng;
-    camera_sample(sc, pass, sample_id, dir, rng);
-    start_path(sc, sample_id, dir, rng, ps);
+    camera_sample<VIEWS>(sc, pass, sample_id, dir, rng);
+    start_path<VIEWS>(sc, pass, sample_id, dir, rng, ps);
 }
 
 // One wavefront step for one path: everything path_tracing() does between the return of one intersect() and the
@@ -979,10 +1027,12 @@ LJ_HD bool shade_path_body(const DScene &sc, uint64_t inc, PathState &ps, ShadeC
     return true;
 }
 // the per-(pixel, sample) schedule: the stream of sample ps.sample of the pass
-template <class Ft = FeatAll>
+template <class Ft = FeatAll, bool VIEWS = false>
 LJ_HD bool shade_path(const DScene &sc, const DPass &pass, PathState &ps, ShadeCounters &cnt) {
     const uint32_t pix_i = fast_div(ps.sample, pass.by_spp);
-    const uint64_t inc = pcg32_inc((uint64_t)pass.pixel_list[pix_i] * pass.spp + (ps.sample - pix_i * pass.spp));
+    uint32_t pixel = pass.pixel_list[pix_i];
+    if constexpr (VIEWS) pixel = view_decode(pass, pixel).pixel;   // the stream of the pixel inside its view
+    const uint64_t inc = pcg32_inc((uint64_t)pixel * pass.spp + (ps.sample - pix_i * pass.spp));
     return shade_path_body<Ft, false>(sc, inc, ps, cnt);
 }
 

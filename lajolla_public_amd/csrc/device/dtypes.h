@@ -228,8 +228,15 @@ struct DPass {
     DFastDiv by_spp, by_width;   // (set_pass_divisors)
     uint64_t seed;
     float *sample_rgb;           // 3 floats per sample of the pass: per-sample radiance (written once per sample)
+    // a batch of cameras (lj_render_views): the frame is n_views x h rows tall and a list entry is e = v*w*h + y*w + x; `views` is the
+    // table of the batch's cameras, by_height / view_pixels (= w*h) decode e (dshade.h view_decode).  Null (a value-initialised DPass):
+    // one camera, DScene::cam, and a list entry is y*w + x
+    const DCamera *views;
+    DFastDiv by_height;
+    uint32_t view_pixels;
 };
 inline void set_pass_divisors(DPass &p, uint32_t spp, uint32_t width) { p.spp = spp; p.by_spp = make_fast_div(spp); p.by_width = make_fast_div(width); }
+inline void set_pass_views(DPass &p, const DCamera *views, uint32_t width, uint32_t height) { p.views = views; p.by_height = make_fast_div(height); p.view_pixels = width * height; }
 
 // the per-tile schedule (LJ_RNG_TILE, dtile.h): one launch's (or one host walk's) view of the job
 struct DTileJob {

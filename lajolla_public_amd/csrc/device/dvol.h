@@ -201,9 +201,9 @@ LJ_HD f3 vol_nee(const DScene &sc, Tracer &tr, VolRng &rng, f3 p, int current_me
 
 // vol_path_tracing_1 (vol_path_tracing.h:6-41): absorption only — a directly visible emitter through the exterior medium of its surface
 template <class Ft, class Tracer>
-LJ_HD f3 vol_path_sample_1(const DScene &sc, Tracer &tr, int x, int y, VolRng &rng) {
+LJ_HD f3 vol_path_sample_1(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, VolRng &rng) {
     const float jy = vrnd(rng), jx = vrnd(rng);
-    const f3 org = ld3(sc.cam.org), dir = camera_primary_dir(sc.cam, x, y, jx, jy);
+    const f3 org = ld3(cam.org), dir = camera_primary_dir(cam, x, y, jx, jy);
     float t, hu, hv; int gprim;
     if (!tr.closest(org, dir, 0.0f, INFINITY, t, hu, hv, gprim)) return mk3(0, 0, 0);   // (sample_primary's tnear: camera.cpp:46)
     const DVertex vertex = build_vertex(sc, org, dir, t, hu, hv, gprim, 0.0f);
@@ -220,9 +220,9 @@ LJ_HD f3 vol_path_sample_1(const DScene &sc, Tracer &tr, int x, int y, VolRng &r
 // vol_path_tracing_2 (vol_path_tracing.h:46-147): one monochromatic homogeneous medium, single scattering, free flight on the red channel
 // (oracle/lj_oracle.cpp vol_path_tracing_2 lists what is kept of the reference's reading of an empty optional)
 template <class Ft, class Tracer>
-LJ_HD f3 vol_path_sample_2(const DScene &sc, Tracer &tr, int x, int y, VolRng &rng) {
+LJ_HD f3 vol_path_sample_2(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, VolRng &rng) {
     const float jy = vrnd(rng), jx = vrnd(rng);
-    const f3 org = ld3(sc.cam.org), dir = camera_primary_dir(sc.cam, x, y, jx, jy);
+    const f3 org = ld3(cam.org), dir = camera_primary_dir(cam, x, y, jx, jy);
     float th, hu, hv; int gprim;
     const bool hit = tr.closest(org, dir, 0.0f, INFINITY, th, hu, hv, gprim);
     DVertex vertex;
@@ -287,14 +287,15 @@ struct VolPath {
 };
 // returns false when the sample is already finished (`result`): versions 1 and 2 are single-shot estimators
 // `rng`: the stream the sample draws from, at its current position (the per-tile schedule hands over the tile's stream, dtile.h)
+// `cam`: the camera the sample belongs to — the scene's, or the entry of a batch's table (DPass::views)
 template <class Ft, class Tracer>
-LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, VolRng rng, VolPath &P, f3 &result) {
+LJ_HD bool vol_path_begin(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, VolRng rng, VolPath &P, f3 &result) {
     P.rng = rng;
     P.bounce_iterations = 0; P.guard = 0;
-    if (sc.vol_path_version == 1) { result = vol_path_sample_1<Ft>(sc, tr, x, y, P.rng); return false; }
-    if (sc.vol_path_version == 2) { result = vol_path_sample_2<Ft>(sc, tr, x, y, P.rng); return false; }
+    if (sc.vol_path_version == 1) { result = vol_path_sample_1<Ft>(sc, cam, tr, x, y, P.rng); return false; }
+    if (sc.vol_path_version == 2) { result = vol_path_sample_2<Ft>(sc, cam, tr, x, y, P.rng); return false; }
     const float jy = vrnd(P.rng), jx = vrnd(P.rng);
-    P.org = ld3(sc.cam.org); P.dir = camera_primary_dir(sc.cam, x, y, jx, jy);
+    P.org = ld3(cam.org); P.dir = camera_primary_dir(cam, x, y, jx, jy);
     P.spread = 0.0f;
     P.current_medium = sc.cam_medium;
     P.throughput = mk3(1, 1, 1); P.radiance = mk3(0, 0, 0);
@@ -304,11 +305,28 @@ LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, VolRng rng
     P.eta_scale = 1.0f;
     return true;
 }
+template <class Ft, class Tracer>
+LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, VolRng rng, VolPath &P, f3 &result) { return vol_path_begin<Ft>(sc, sc.cam, tr, x, y, rng, P, result); }
 // the per-(pixel, sample) schedule: a fresh stream per sample
 template <class Ft, class Tracer>
-LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, uint64_t stream, uint64_t seed, VolPath &P, f3 &result) {
+LJ_HD bool vol_path_begin(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, uint64_t stream, uint64_t seed, VolPath &P, f3 &result) {
     VolRng rng; rng.inc = pcg32_inc(stream); rng.state = pcg32_init(stream, seed);
-    return vol_path_begin<Ft>(sc, tr, x, y, rng, P, result);
+    return vol_path_begin<Ft>(sc, cam, tr, x, y, rng, P, result);
+}
+template <class Ft, class Tracer>
+LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, uint64_t stream, uint64_t seed, VolPath &P, f3 &result) {
+    return vol_path_begin<Ft>(sc, sc.cam, tr, x, y, stream, seed, P, result);
+}
+// camera sample `sample` of a pass (k_volpath and its host twin): pixel, stream and — for a batch of cameras — the view from the list entry
+template <class Ft, bool VIEWS, class Tracer>
+LJ_HD bool vol_path_begin_sample(const DScene &sc, const DPass &pass, Tracer &tr, uint32_t sample, VolPath &P, f3 &result) {
+    const uint32_t p = fast_div(sample, pass.by_spp), k = sample - p * pass.spp;
+    const uint32_t pixel = pass.pixel_list[p];
+    if constexpr (VIEWS) {
+        const ViewPixel vp = view_decode(pass, pixel);
+        return with_view_camera(pass, vp.view, [&](const DCamera &cam) { return vol_path_begin<Ft>(sc, cam, tr, vp.x, vp.y, (uint64_t)vp.pixel * pass.spp + k, pass.seed, P, result); });
+    }
+    else return vol_path_begin<Ft>(sc, tr, (int)(pixel - fast_div(pixel, pass.by_width) * (uint32_t)sc.cam.width), (int)fast_div(pixel, pass.by_width), (uint64_t)pixel * pass.spp + k, pass.seed, P, result);
 }
 // one iteration of the loop; false: the path has ended with `result`
 template <class Ft, class Tracer>

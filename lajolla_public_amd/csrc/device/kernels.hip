@@ -240,7 +240,7 @@ template <class Ft> struct ShadeSorted { static constexpr bool value = Ft::envma
 // Sorted feature sets: within a chunk, thread t takes the t-th path in (key, slot) order — a counting sort by wave ballots, one LDS
 // table of counts and one of slots — so that a wave's lanes run the same branch of shade_path; the survivors are then compacted in that
 // order.  A path's value does not depend on where it sits in the queue (its radiance goes to sample_rgb[sample]), so images are unchanged.
-template <class Ft>
+template <class Ft, bool VIEWS>
 __device__ __forceinline__ uint32_t shade_compact_segment(const DScene &sc, const DPass &pass, const DQueue &q, uint32_t base, uint32_t count, ShadeCounters &cnt, uint32_t (*s_oct)[kBlock / 64], bool octant_bin = false) {
     constexpr bool SORT = ShadeSorted<Ft>::value;
     __shared__ uint16_t s_perm[SORT ? kBlock : 1];
@@ -278,7 +278,7 @@ __device__ __forceinline__ uint32_t shade_compact_segment(const DScene &sc, cons
         PathState ps;
         if (j < count) {
             q_load_for_shade(q, base + j, ps);
-            alive = shade_path<Ft>(sc, pass, ps, cnt);
+            alive = shade_path<Ft, VIEWS>(sc, pass, ps, cnt);
             if (!alive) {
                 float *o = pass.sample_rgb + 3ull * ps.sample;
                 o[0] = ps.rad.x; o[1] = ps.rad.y; o[2] = ps.rad.z;
@@ -303,7 +303,7 @@ __device__ __forceinline__ uint32_t shade_compact_segment(const DScene &sc, cons
 // `sb.perm` (key-major), (3) shading in that order — reading the queue records of slot perm[t] from `q` and writing the survivors,
 // compacted, to `qo`: a SECOND set of queue records, because a path read from anywhere in the segment may not be overwritten by an
 // earlier survivor.  The extend launch that follows works on `qo`; the two sets swap roles every step.
-template <class Ft>
+template <class Ft, bool VIEWS>
 __device__ __forceinline__ uint32_t shade_sorted_segment(const DScene &sc, const DPass &pass, const DQueue &q, const DQueue &qo, const ShadeSortBuf &sb, uint32_t base, uint32_t count,
                                                          ShadeCounters &cnt, uint32_t (*s_oct)[kBlock / 64]) {
     __shared__ uint32_t s_start[kShadeKeys];
@@ -360,7 +360,7 @@ __device__ __forceinline__ uint32_t shade_sorted_segment(const DScene &sc, const
         if (t < count) {
             const uint32_t j = sb.perm[base + t];
             q_load_for_shade(q, base + j, ps);
-            alive = shade_path<Ft>(sc, pass, ps, cnt);
+            alive = shade_path<Ft, VIEWS>(sc, pass, ps, cnt);
             if (!alive) {
                 float *o = pass.sample_rgb + 3ull * ps.sample;
                 o[0] = ps.rad.x; o[1] = ps.rad.y; o[2] = ps.rad.z;
@@ -390,7 +390,7 @@ template <> struct ShadeOccupancy<FeatLambert> { static constexpr int waves = LJ
 template <> struct ShadeOccupancy<FeatLambertTex> { static constexpr int waves = LJ_SHADE_OCC_LARGE; };
 template <> struct ShadeOccupancy<FeatDisney> { static constexpr int waves = LJ_SHADE_OCC_LARGE; };
 
-template <class Ft, int STAGE>
+template <class Ft, int STAGE, bool VIEWS>
 __global__ void __launch_bounds__(kBlock, ShadeOccupancy<Ft>::waves) k_shade(DScene sc, DPass pass, DQueue q, DQueue qo, ShadeSortBuf sb, DBlockState *blocks, uint32_t seg, ShadeStage stg, uint32_t *work, uint32_t *chunk_list, uint32_t parity, uint32_t extend_waves) {
     __shared__ uint32_t s_list_base;
     if (blockIdx.x == 0 && threadIdx.x == 0) work[0] = extend_waves;   // the extend launch that follows draws list entries beyond its own waves from it
@@ -406,14 +406,14 @@ __global__ void __launch_bounds__(kBlock, ShadeOccupancy<Ft>::waves) k_shade(DSc
     // ---- shade the live front of the segment chunk by chunk; survivors are compacted to the front, in order
     // (qo: the record set the survivors go to — `q` itself unless the segment is sorted as a whole, shade_sorted_segment)
     uint32_t out;
-    if (ShadeSorted<Ft>::value && sb.perm != nullptr) out = shade_sorted_segment<Ft>(sc, pass, q, qo, sb, base, count, cnt, s_wcnt);
-    else out = shade_compact_segment<Ft>(sc, pass, q, base, count, cnt, s_wcnt, sb.octant_bin != 0u);
+    if (ShadeSorted<Ft>::value && sb.perm != nullptr) out = shade_sorted_segment<Ft, VIEWS>(sc, pass, q, qo, sb, base, count, cnt, s_wcnt);
+    else out = shade_compact_segment<Ft, VIEWS>(sc, pass, q, base, count, cnt, s_wcnt, sb.octant_bin != 0u);
     // ---- refill the rest of the segment with the workgroup's next camera samples (path_tracing.h:10-14)
     const uint32_t left = end_sample - next_sample, room = seg - out;
     const uint32_t n_new = left < room ? left : room;
     for (uint32_t g = threadIdx.x; g < n_new; g += kBlock) {
         PathState ps;
-        generate_path(sc, pass, next_sample + g, ps);
+        generate_path<VIEWS>(sc, pass, next_sample + g, ps);
         q_store(qo, base + out + g, ps);
     }
     const uint32_t b = wave_sum(cnt.bounces), cl = wave_sum(cnt.closest), sh = wave_sum(cnt.shadow), dn = wave_sum(cnt.done);
@@ -439,7 +439,7 @@ __global__ void __launch_bounds__(kBlock, ShadeOccupancy<Ft>::waves) k_shade(DSc
 // overhead (~10 us each, tens of bounces).  A workgroup's segment is independent of every other one, so the rest of the
 // render runs inside ONE launch: each workgroup alternates "trace my live paths" and "shade + compact my segment" until
 // its segment is empty.  Per-sample values are the same as with separate launches, bit for bit.
-template <class Ft>
+template <class Ft, bool VIEWS>
 __global__ void __launch_bounds__(kBlock, 2) k_tail(DScene sc, DPass pass, DQueue q, DBlockState *blocks, uint32_t seg, ShadeStage stg, uint32_t shade_lds_at,
                                                     int stack, int lds_nodes, int lds_prims, int *spill) {
     __shared__ uint32_t s_wcnt[16][kBlock / 64];   // two tables of (octant x wave) survivor counts, used alternately
@@ -486,7 +486,7 @@ __global__ void __launch_bounds__(kBlock, 2) k_tail(DScene sc, DPass pass, DQueu
         __syncthreads();   // (workgroup-scope release/acquire of the records just written)
         // ---- shade + compact
         path_steps += count;
-        count = shade_compact_segment<Ft>(ssc, pass, q, base, count, cnt, s_wcnt);
+        count = shade_compact_segment<Ft, VIEWS>(ssc, pass, q, base, count, cnt, s_wcnt);
         __syncthreads();
     }
     __shared__ unsigned long long s_cnt[4];
@@ -584,12 +584,20 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays(DScene sc, const RayIO *r
 
 // ---------------------------------------------------------------- auxiliary buffers (render.cpp:12-69)
 // One thread per listed pixel: primary ray through the pixel centre, closest hit, aux_value().
-__global__ void __launch_bounds__(kBlock) k_aux(DScene sc, const uint32_t *pixel_list, uint32_t n_pixels, int integrator, float *rgb, int stack, int lds_nodes, int lds_prims, int *spill) {
+// (pass: the pixel list, and for a batch of cameras — VIEWS — the table the list's entries are decoded with; no sample buffer, nothing is drawn)
+template <bool VIEWS>
+__global__ void __launch_bounds__(kBlock) k_aux(DScene sc, DPass pass, uint32_t n_pixels, int integrator, float *rgb, int stack, int lds_nodes, int lds_prims, int *spill) {
     const TreeView tv = stage_tree(sc, stack, lds_nodes, lds_prims, spill, gridDim.x * kBlock, blockIdx.x * kBlock + threadIdx.x);
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_pixels; i += gridDim.x * kBlock) {
-        const uint32_t pixel = pixel_list[i];
-        const int x = (int)(pixel % (uint32_t)sc.cam.width), y = (int)(pixel / (uint32_t)sc.cam.width);
-        const f3 org = ld3(sc.cam.org), dir = camera_primary_dir(sc.cam, x, y, 0.5f, 0.5f);
+        const uint32_t pixel = pass.pixel_list[i];
+        f3 org, dir;
+        if constexpr (VIEWS) {
+            const ViewPixel vp = view_decode(pass, pixel);
+            with_view_camera(pass, vp.view, [&](const DCamera &cam) { org = ld3(cam.org); dir = camera_primary_dir(cam, vp.x, vp.y, 0.5f, 0.5f); return 0; });
+        } else {
+            const int x = (int)(pixel % (uint32_t)sc.cam.width), y = (int)(pixel / (uint32_t)sc.cam.width);
+            org = ld3(sc.cam.org); dir = camera_primary_dir(sc.cam, x, y, 0.5f, 0.5f);
+        }
         LaneTrav L;
         L.ray.ox = org.x; L.ray.oy = org.y; L.ray.oz = org.z; L.ray.dx = dir.x; L.ray.dy = dir.y; L.ray.dz = dir.z;
         trav_begin(L, 0.0f, INFINITY);   // camera.cpp:46: tnear 0
@@ -735,10 +743,12 @@ void launch_shade(const DScene &sc, const DPass &pass, const DQueue &q, const DQ
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kBlock), cfg.smem, s, sc, pass, q, qo, sb, blocks, seg, st, work, chunk_list, parity, extend_waves); };
     // (a scene whose tables are not staged at all runs the all-features instantiation: lj_scene_upload picks it)
     const int stage = cfg.smem == 0 ? 0 : (cfg.stage_prims ? 2 : 1);
-    if (stage == 0) { launch(k_shade<FeatAll, 0>); return; }
+    // (a batch of cameras, DPass::views, runs the VIEWS instantiations: dshade.h)
+    if (stage == 0) { if (pass.views) launch(k_shade<FeatAll, 0, true>); else launch(k_shade<FeatAll, 0, false>); return; }
     with_shade_variant(cfg.variant, [&](auto ft) {
         using Ft = decltype(ft);
-        if (stage == 2) launch(k_shade<Ft, 2>); else launch(k_shade<Ft, 1>);
+        if (pass.views) { if (stage == 2) launch(k_shade<Ft, 2, true>); else launch(k_shade<Ft, 1, true>); }
+        else if (stage == 2) launch(k_shade<Ft, 2, false>); else launch(k_shade<Ft, 1, false>);
     });
 }
 // LDS the fused tail needs: the extend image followed by the shade tables; 0 when that does not fit one workgroup's share
@@ -751,15 +761,15 @@ void launch_tail(const DScene &sc, const DPass &pass, const DQueue &q, DBlockSta
     const uint32_t at = (uint32_t)((ecfg.smem + 15) & ~(size_t)15);
     const size_t smem = tail_smem(ecfg, scfg);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kBlock), smem, s, sc, pass, q, blocks, seg, st, at, ecfg.stack, ecfg.lds_nodes, ecfg.lds_prims, spill); };
-    with_shade_variant(scfg.variant, [&](auto ft) { launch(k_tail<decltype(ft)>); });
+    with_shade_variant(scfg.variant, [&](auto ft) { if (pass.views) launch(k_tail<decltype(ft), true>); else launch(k_tail<decltype(ft), false>); });
 }
 void launch_resolve(const DPass &pass, uint32_t n_pixels, float *rgb, hipStream_t s) {
     const uint32_t waves_per_block = kBlock / 64;
     const uint32_t grid = (n_pixels + waves_per_block - 1) / waves_per_block;
     if (grid) hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(kBlock), 0, s, pass, n_pixels, rgb);
 }
-void launch_aux(const DScene &sc, const uint32_t *pixel_list, uint32_t n_pixels, int integrator, float *rgb, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s) {
-    if (n_pixels) hipLaunchKernelGGL(k_aux, dim3(grid), dim3(kBlock), cfg.smem, s, sc, pixel_list, n_pixels, integrator, rgb, cfg.stack, cfg.lds_nodes, cfg.lds_prims, spill);
+void launch_aux(const DScene &sc, const DPass &pass, uint32_t n_pixels, int integrator, float *rgb, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s) {
+    if (n_pixels) hipLaunchKernelGGL(pass.views ? k_aux<true> : k_aux<false>, dim3(grid), dim3(kBlock), cfg.smem, s, sc, pass, n_pixels, integrator, rgb, cfg.stack, cfg.lds_nodes, cfg.lds_prims, spill);
 }
 void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s) {
     if (cfg.wide) { launch_trace_rays8(sc, rays, n, hits, occ, cfg, spill, grid, s); return; }

@@ -216,9 +216,11 @@ __device__ __forceinline__ void opaque_state(PathState &ps) {
 }
 
 // A dead lane starts the path of stash slot `slot` (generated by whichever lane had that index; same values as generate_path on this lane)
-__device__ __forceinline__ void stash_start(const DScene &sc, const ScanCtx &sx, uint32_t st_base, uint32_t slot, PathState &ps) {
+// (a batch of cameras: the stash holds no origin — start_path finds the sample's view from its id and reads the origin from the table)
+template <bool VIEWS>
+__device__ __forceinline__ void stash_start(const DScene &sc, const DPass &pass, const ScanCtx &sx, uint32_t st_base, uint32_t slot, PathState &ps) {
     const f3 dir = mk3(sx.st_dir[slot], sx.st_dir[64 + slot], sx.st_dir[128 + slot]);
-    start_path(sc, st_base + slot, dir, sx.st_rng[slot], ps);
+    start_path<VIEWS>(sc, pass, st_base + slot, dir, sx.st_rng[slot], ps);
 }
 
 // LDS image of the scan area at byte offset `at` (16-byte aligned): [leaf table][primitives, transposed][4 x wave scratch]
@@ -269,7 +271,8 @@ template <class Ft> constexpr bool mega_stash() { return LJ_MEGA_STASH && MegaOc
 template <class Ft> constexpr uint32_t mega_item_cap() { return (mega_stash<Ft>() || (LJ_MEGA_ITEM_CAP_TIGHT && MegaOccupancy<Ft>::waves >= 5)) ? kItemCapTight : kItemCap; }
 
 // stats: [0] bounce iterations, [1] closest-hit rays, [2] shadow rays, [3] samples finished, [4] path steps (shade_path calls)
-template <class Ft, bool SPHERES>
+// (VIEWS: the pass is a batch of cameras, dshade.h; same occupancy, same LDS — the stash has no per-view entry)
+template <class Ft, bool SPHERES, bool VIEWS>
 __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScene sc, DPass pass, ShadeStage stg, uint32_t scan_at, uint32_t n_samples, uint32_t grab,
                                                               uint32_t *sample_counter, unsigned long long *stats) {
     stage_shade_tables<2>(sc, stg, 0u);
@@ -288,7 +291,7 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
         opaque_state(ps);
         if (live) {
             steps++;
-            if (!shade_path<Ft>(sc, pass, ps, cnt)) {
+            if (!shade_path<Ft, VIEWS>(sc, pass, ps, cnt)) {
                 float *o = pass.sample_rgb + 3ull * ps.sample;
                 o[0] = ps.rad.x; o[1] = ps.rad.y; o[2] = ps.rad.z;
                 cnt.done++; live = false;
@@ -305,7 +308,7 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
                 uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
                 uint32_t first;
                 uint32_t take = regen_take(rg, n_dead, first);
-                if (!live && rank < take) { stash_start(sc, sx, rg.st_base, first + rank, ps); live = true; }
+                if (!live && rank < take) { stash_start<VIEWS>(sc, pass, sx, rg.st_base, first + rank, ps); live = true; }
                 n_dead -= take; rank -= take;   // (rank of a lane that is still dead among those still dead)
                 if (n_dead != 0u) {
                     if (regen_needs_grab(rg)) {
@@ -318,12 +321,12 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();   // the reads above come first
                         if (lane < n_gen) {
                             f3 dir; uint64_t rng;
-                            camera_sample(sc, pass, rg.st_base + lane, dir, rng);
+                            camera_sample<VIEWS>(sc, pass, rg.st_base + lane, dir, rng);
                             sx.st_rng[lane] = rng; sx.st_dir[lane] = dir.x; sx.st_dir[64 + lane] = dir.y; sx.st_dir[128 + lane] = dir.z;
                         }
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
                         take = regen_take(rg, n_dead, first);
-                        if (!live && rank < take) { stash_start(sc, sx, rg.st_base, first + rank, ps); live = true; }
+                        if (!live && rank < take) { stash_start<VIEWS>(sc, pass, sx, rg.st_base, first + rank, ps); live = true; }
                     }
                 }
             }
@@ -343,7 +346,7 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
                 if (!rg.exhausted) {
                     const uint32_t left = rg.w_end - rg.w_next, n_dead = (uint32_t)__popcll(dead);
                     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
-                    if (!live && rank < left) { generate_path(sc, pass, rg.w_next + rank, ps); live = true; }
+                    if (!live && rank < left) { generate_path<VIEWS>(sc, pass, rg.w_next + rank, ps); live = true; }
                     rg.w_next += n_dead < left ? n_dead : left;
                 }
             }
@@ -427,8 +430,10 @@ void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, b
     const size_t smem = mega_smem(sc, scfg);
     with_shade_variant(scfg.variant, [&](auto ft) {
         using Ft = decltype(ft);
-        if (spheres) hipLaunchKernelGGL((k_mega<Ft, true>), dim3(grid), dim3(kBlock), smem, s, sc, pass, st, at, n_samples, grab, sample_counter, stats);
-        else hipLaunchKernelGGL((k_mega<Ft, false>), dim3(grid), dim3(kBlock), smem, s, sc, pass, st, at, n_samples, grab, sample_counter, stats);
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), smem, s, sc, pass, st, at, n_samples, grab, sample_counter, stats); };
+        if (pass.views) { if (spheres) launch(k_mega<Ft, true, true>); else launch(k_mega<Ft, false, true>); }
+        else if (spheres) launch(k_mega<Ft, true, false>);
+        else launch(k_mega<Ft, false, false>);
     });
 }
 

@@ -35,6 +35,18 @@ void lj_host_scene_free(lj_host_scene *hs) {
     delete hs;
 }
 
+int lj_camera_look_at(const double origin[3], const double target[3], const double up[3], double fov,
+                      int32_t width, int32_t height, int32_t filter_kind, double filter_param, LjCamera *out) {
+    return lj::guard([&]() {
+        if (!origin || !target || !up || !out) throw lj::LjError(LJ_ERR_INVALID_ARG, "lj_camera_look_at: null argument");
+        if (width <= 0 || height <= 0) throw lj::LjError(LJ_ERR_INVALID_ARG, "lj_camera_look_at: bad film size");
+        if (filter_kind < LJ_FILTER_BOX || filter_kind > LJ_FILTER_GAUSSIAN) throw lj::LjError(LJ_ERR_INVALID_ARG, "lj_camera_look_at: unknown filter kind");
+        // (a <lookat> inside an otherwise empty <transform name="toWorld">: scene_xml.cpp parse_transform multiplies it onto the identity)
+        const lj::M4 to_world = lj::look_at({origin[0], origin[1], origin[2]}, {target[0], target[1], target[2]}, {up[0], up[1], up[2]}) * lj::M4::identity();
+        *out = lj::make_camera(to_world, fov, width, height, filter_kind, filter_param);
+    });
+}
+
 int lj_image_write(const char *filename, int32_t width, int32_t height, const float *rgb) {
     return lj::guard([&]() {
         if (!filename || !rgb) throw lj::LjError(LJ_ERR_INVALID_ARG, "lj_image_write: null argument");

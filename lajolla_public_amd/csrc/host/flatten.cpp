@@ -109,6 +109,26 @@ ljd::DScene FlatScene::host_view() const {
     return s;
 }
 
+// numbers the kernels index memory with must be finite: a NaN in a camera matrix turns into NaN directions and from there into texel /
+// table indices on the device (the reference has the same hole; a GPU fault is a worse failure)
+void check_camera(const LjCamera &c) {
+    auto finite = [](const double *v, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; };
+    if (!finite(c.cam_to_world, 16) || !finite(c.sample_to_cam, 16) || !std::isfinite(c.filter_param))
+        throw LjError(LJ_ERR_INVALID_ARG, "camera: matrix or filter parameter is not finite");
+    if (c.width <= 0 || c.height <= 0 || (long long)c.width * c.height > (1ll << 28)) throw LjError(LJ_ERR_INVALID_ARG, "camera: bad film size");
+}
+
+ljd::DCamera flatten_camera(const LjCamera &c) {
+    ljd::DCamera o{};
+    for (int i = 0; i < 16; i++) { o.sample_to_cam[i] = (float)c.sample_to_cam[i]; o.cam_to_world[i] = (float)c.cam_to_world[i]; }
+    {   // xform_point(cam_to_world, 0) (camera.cpp:44)
+        const double *m = c.cam_to_world; double inv_w = 1.0 / m[15];
+        o.org[0] = (float)(m[3] * inv_w); o.org[1] = (float)(m[7] * inv_w); o.org[2] = (float)(m[11] * inv_w);
+    }
+    o.width = c.width; o.height = c.height; o.filter_kind = c.filter_kind; o.filter_param = (float)c.filter_param;
+    return o;
+}
+
 FlatScene flatten_scene(const LjSceneDesc &d) {
     FlatScene F;
     if (d.options.integrator < LJ_INTEGRATOR_DEPTH || d.options.integrator > LJ_INTEGRATOR_VOLPATH)
@@ -118,9 +138,7 @@ FlatScene flatten_scene(const LjSceneDesc &d) {
     // directions and from there into texel / table indices on the device (the reference has the same hole; a GPU fault is a worse failure)
     {
         auto finite = [](const double *v, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; };
-        if (!finite(d.camera.cam_to_world, 16) || !finite(d.camera.sample_to_cam, 16) || !std::isfinite(d.camera.filter_param))
-            throw LjError(LJ_ERR_INVALID_ARG, "camera: matrix or filter parameter is not finite");
-        if (d.camera.width <= 0 || d.camera.height <= 0 || (long long)d.camera.width * d.camera.height > (1ll << 28)) throw LjError(LJ_ERR_INVALID_ARG, "camera: bad film size");
+        check_camera(d.camera);
         if (d.n_vertices > 0 && (!d.positions || !finite(d.positions, (size_t)d.n_vertices * 3))) throw LjError(LJ_ERR_INVALID_ARG, "a vertex position is not finite");
         for (int i = 0; i < d.n_shapes; i++) {
             const LjShape &sh = d.shapes[i];
@@ -170,12 +188,7 @@ FlatScene flatten_scene(const LjSceneDesc &d) {
     F.integrator = d.options.integrator; F.spp = d.options.samples_per_pixel; F.max_depth = d.options.max_depth; F.rr_depth = d.options.rr_depth;
     F.envmap_light_id = d.envmap_light_id;
     // ---- camera
-    for (int i = 0; i < 16; i++) { F.cam.sample_to_cam[i] = (float)d.camera.sample_to_cam[i]; F.cam.cam_to_world[i] = (float)d.camera.cam_to_world[i]; }
-    {   // xform_point(cam_to_world, 0) (camera.cpp:44)
-        const double *m = d.camera.cam_to_world; double inv_w = 1.0 / m[15];
-        F.cam.org[0] = (float)(m[3] * inv_w); F.cam.org[1] = (float)(m[7] * inv_w); F.cam.org[2] = (float)(m[11] * inv_w);
-    }
-    F.cam.width = d.camera.width; F.cam.height = d.camera.height; F.cam.filter_kind = d.camera.filter_kind; F.cam.filter_param = (float)d.camera.filter_param;
+    F.cam = flatten_camera(d.camera);
 
     // ---- materials
     for (int i = 0; i < d.n_materials; i++) {

@@ -41,6 +41,12 @@ struct FlatScene {
     ljd::DScene host_view() const;
 };
 
+// One camera, as flatten_scene treats the scene's: check_camera throws LjError(LJ_ERR_INVALID_ARG) for a matrix or filter parameter that is
+// not finite and for a bad film size; flatten_camera is the conversion that fills FlatScene::cam (lj_scene_set_camera and the camera
+// table of lj_render_views go through the same two).
+void check_camera(const LjCamera &c);
+ljd::DCamera flatten_camera(const LjCamera &c);
+
 // Throws LjError(LJ_ERR_UNSUPPORTED) for variant alternatives the device path does not implement.
 FlatScene flatten_scene(const LjSceneDesc &d);
 

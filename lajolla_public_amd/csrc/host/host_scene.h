@@ -49,6 +49,19 @@ struct HostScene {
     void finalize();
 };
 
+// Camera::Camera (camera.cpp:7-21); fov in degrees along x.  The XML front end (scene_xml.cpp parse_sensor) and lj_camera_look_at build their
+// cameras here, so the two agree to the bit.
+inline LjCamera make_camera(const M4 &cam_to_world, double fov, int width, int height, int filter_kind, double filter_param) {
+    LjCamera cam{};
+    auto store = [](double dst[16], const M4 &m) { for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) dst[i * 4 + j] = m(i, j); };
+    double aspect = (double)width / (double)height;
+    M4 cam_to_sample = scale({-0.5, -0.5 * aspect, 1.0}) * translate({-1.0, -1.0 / aspect, 0.0}) * perspective(fov);
+    store(cam.cam_to_world, cam_to_world); store(cam.world_to_cam, inverse(cam_to_world));
+    store(cam.cam_to_sample, cam_to_sample); store(cam.sample_to_cam, inverse(cam_to_sample));
+    cam.width = width; cam.height = height; cam.filter_kind = filter_kind; cam.filter_param = filter_param; cam.medium_id = -1;
+    return cam;
+}
+
 // deep copy of a caller-provided description
 HostScene *host_scene_from_desc(const LjSceneDesc &d);
 
