@@ -331,6 +331,20 @@ typedef struct LjFrameQuery { float n[3], v[3]; } LjFrameQuery;
 typedef struct LjFrameResult { float x[3], y[3], to_local[3], to_world[3]; } LjFrameResult;
 int lj_frame_queries(lj_context *ctx, int64_t n, const LjFrameQuery *queries_host, LjFrameResult *results_host);
 
+/* eval(phase_function, dir_in, dir_out) — which is also pdf_sample_phase — and sample_phase_function(phase_function, dir_in, rnd)
+ * (phase_function.h:18-30, isotropic.inl and henyeygreenstein.inl) of the device code the volumetric path tracer runs
+ * (device/dvol.h phase_eval / phase_sample); no scene needed.  phase_kind: LJ_PHASE_*; g: HenyeyGreenstein::g (ignored when isotropic). */
+typedef struct LjPhaseQuery { int32_t phase_kind; float g, dir_in[3], dir_out[3], rnd[2]; } LjPhaseQuery;
+typedef struct LjPhaseResult { float eval, sample[3]; } LjPhaseResult;
+int lj_phase_queries(lj_context *ctx, int64_t n, const LjPhaseQuery *queries_host, LjPhaseResult *results_host);
+
+/* get_sigma_s(medium, p) and get_sigma_a(medium, p) at the point p, and get_majorant(medium, ray) for the ray (org, dir, tfar)
+ * (medium.h:25-27, media/heterogeneous.inl; the grid volume's trilinear lookup and box test, volume.h:39-81, 118-144) of medium `medium_id` of the
+ * scene, by device/dvol.h get_sigmas / get_majorant.  LJ_ERR_INVALID_ARG: a medium_id outside the scene's media. */
+typedef struct LjMediumQuery { int32_t medium_id; float p[3], org[3], dir[3], tfar; } LjMediumQuery;
+typedef struct LjMediumResult { float sigma_s[3], sigma_a[3], majorant[3]; } LjMediumResult;
+int lj_medium_queries(lj_scene *scene, int64_t n, const LjMediumQuery *queries_host, LjMediumResult *results_host);
+
 /* Counters of the last lj_render* call. */
 typedef struct LjStats {
     uint64_t samples;          /* camera samples traced (LJ_RNG_TILE: those of every tile walked, outside a crop window too) */

@@ -298,6 +298,8 @@ PRIMARY_QUERY, PRIMARY_RESULT = np.dtype(_abi.LjPrimaryQuery), np.dtype(_abi.LjP
 FILTER_QUERY = np.dtype(_abi.LjFilterQuery)
 TEXTURE_QUERY = np.dtype(_abi.LjTextureQuery)
 FRAME_QUERY, FRAME_RESULT = np.dtype(_abi.LjFrameQuery), np.dtype(_abi.LjFrameResult)
+PHASE_QUERY, PHASE_RESULT = np.dtype(_abi.LjPhaseQuery), np.dtype(_abi.LjPhaseResult)
+MEDIUM_QUERY, MEDIUM_RESULT = np.dtype(_abi.LjMediumQuery), np.dtype(_abi.LjMediumResult)
 
 
 def _vp(a):
@@ -381,6 +383,22 @@ def frame_queries(ctx, queries):
     q = _q(queries, FRAME_QUERY)
     r = np.zeros(q.shape[0], FRAME_RESULT)
     _check(load_library().lj_frame_queries(ctx._h, q.shape[0], _vp(q), _vp(r)))
+    return r
+
+
+def phase_queries(ctx, queries):
+    """eval (== pdf_sample_phase) and sample_phase_function of the device phase-function code (dvol.h), per query."""
+    q = _q(queries, PHASE_QUERY)
+    r = np.zeros(q.shape[0], PHASE_RESULT)
+    _check(load_library().lj_phase_queries(ctx._h, q.shape[0], _vp(q), _vp(r)))
+    return r
+
+
+def medium_queries(scene, queries):
+    """get_sigma_s / get_sigma_a at a point and get_majorant along a ray of the device medium code (dvol.h), per query."""
+    q = _q(queries, MEDIUM_QUERY)
+    r = np.zeros(q.shape[0], MEDIUM_RESULT)
+    _check(load_library().lj_medium_queries(scene._h, q.shape[0], _vp(q), _vp(r)))
     return r
 
 

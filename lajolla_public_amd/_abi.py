@@ -191,6 +191,22 @@ class LjFrameResult(C.Structure):
     _fields_ = [("x", C.c_float * 3), ("y", C.c_float * 3), ("to_local", C.c_float * 3), ("to_world", C.c_float * 3)]
 
 
+class LjPhaseQuery(C.Structure):
+    _fields_ = [("phase_kind", C.c_int32), ("g", C.c_float), ("dir_in", C.c_float * 3), ("dir_out", C.c_float * 3), ("rnd", C.c_float * 2)]
+
+
+class LjPhaseResult(C.Structure):
+    _fields_ = [("eval", C.c_float), ("sample", C.c_float * 3)]
+
+
+class LjMediumQuery(C.Structure):
+    _fields_ = [("medium_id", C.c_int32), ("p", C.c_float * 3), ("org", C.c_float * 3), ("dir", C.c_float * 3), ("tfar", C.c_float)]
+
+
+class LjMediumResult(C.Structure):
+    _fields_ = [("sigma_s", C.c_float * 3), ("sigma_a", C.c_float * 3), ("majorant", C.c_float * 3)]
+
+
 # every symbol include/lajolla_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("lj_last_error", C.c_char_p, []),
@@ -228,6 +244,8 @@ SYMBOLS = [
     ("lj_pcg32_queries", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     ("lj_texture_queries", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_frame_queries", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lj_phase_queries", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("lj_medium_queries", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_group_create", C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     ("lj_group_destroy", None, [C.c_void_p]),
     ("lj_group_size", C.c_int, [C.c_void_p]),

@@ -68,7 +68,12 @@ struct Frame3 { f3 x, y, n; };
 LJ_HD void coordinate_system(f3 n, f3 &a_out, f3 &b_out) {
     if (n.z < -1.0f + 1e-6f) { a_out = mk3(0, -1, 0); b_out = mk3(-1, 0, 0); }
     else {
-        float a = 1.0f / (1.0f + n.z), b = -n.x * n.y * a;
+        // a = 1 / (1 + n.z) (frame.h:16).  Towards n.z = -1 that sum keeps only the digits n.z kept when it was rounded to float: the frame of
+        // a direction within 1e-3 of -z came out up to 1e-4 off unit length.  For a unit n the same number is (1 - n.z) / (n.x^2 + n.y^2),
+        // which cancels nothing.
+        const float s = n.x * n.x + n.y * n.y;
+        const bool low = n.z < -0.9f && s > 0.0f;
+        float a = (low ? 1.0f - n.z : 1.0f) / (low ? s : 1.0f + n.z), b = -n.x * n.y * a;
         a_out = mk3(1.0f - n.x * n.x * a, b, -n.x);
         b_out = mk3(b, 1.0f - n.y * n.y * a, -n.y);
     }

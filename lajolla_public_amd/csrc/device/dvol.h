@@ -31,8 +31,11 @@ LJ_HD float vavg3(f3 a) { return (a.x + a.y + a.z) / 3.0f; }
 // lookup(VolumeSpectrum, p) (volume.h:39-81)
 LJ_HD f3 volume_lookup(const DScene &sc, const DVolume &v, f3 p) {
     if (v.kind == 0) return ld3(v.value);
-    f3 pn = vdiv3(p - ld3(v.p_min), ld3(v.p_max) - ld3(v.p_min));
-    if (pn.x < 0.0f || pn.x > 1.0f || pn.y < 0.0f || pn.y > 1.0f || pn.z < 0.0f || pn.z > 1.0f) return mk3(0, 0, 0);
+    // The box test of volume.h:48 is on pn = (p - p_min) / (p_max - p_min).  In float, p - p_min rounds a point one ulp beyond p_max onto the
+    // face (pn == 1: inside), where the reference's doubles see it outside; on p itself the test is the reference's for every float p.
+    const f3 lo = ld3(v.p_min), hi = ld3(v.p_max);
+    if (p.x < lo.x || p.x > hi.x || p.y < lo.y || p.y > hi.y || p.z < lo.z || p.z > hi.z) return mk3(0, 0, 0);
+    f3 pn = vdiv3(p - lo, hi - lo);
     const int rx = v.res[0], ry = v.res[1], rz = v.res[2];
     pn.x *= (float)(rx - 1); pn.y *= (float)(ry - 1); pn.z *= (float)(rz - 1);
     auto clampi = [](int a, int lo, int hi) { return a < lo ? lo : (a > hi ? hi : a); };

@@ -1,11 +1,12 @@
 // Batched per-object queries on the device (include/lajolla_hip.h, "per-object queries"): the reference's free functions
-// on Material / Light / Shape / Camera / Filter / Texture / Frame / pcg32, answered by the very device functions the shade
-// kernels are built from (dshade.h, dmath.h), one query per lane.  They exist so that the HIP shading code can be held value
+// on Material / Light / Shape / Camera / Filter / Texture / Frame / pcg32 / PhaseFunction / Medium, answered by the very device
+// functions the shade kernels are built from (dshade.h, dmath.h, dvol.h), one query per lane.  They exist so that the HIP shading code can be held value
 // for value against vectors the reference's own functions produced (tests/golden/*.json) and so that the reference's
 // unit tests (src/tests/materials.cpp, filter.cpp, frame.cpp, mipmap.cpp) can be re-run against the GPU — instead of
 // meeting the reference only inside whole paths.  No oracle, no CPU arithmetic: the host code here only copies.
 #include "api_internal.h"
 #include "dshade.h"
+#include "dvol.h"
 
 namespace ljd {
 namespace {
@@ -129,6 +130,31 @@ __global__ void __launch_bounds__(kQBlock) k_frame_queries(const LjFrameQuery *q
         const f3 v = ld3(q[i].v);
         LjFrameResult o;
         st3(o.x, f.x); st3(o.y, f.y); st3(o.to_local, to_local(f, v)); st3(o.to_world, to_world(f, v));
+        r[i] = o;
+    }
+}
+
+__global__ void __launch_bounds__(kQBlock) k_phase_queries(const LjPhaseQuery *q, LjPhaseResult *r, long long n) {
+    for (long long i = (long long)blockIdx.x * kQBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kQBlock) {
+        const LjPhaseQuery qi = q[i];
+        DMedium m{};   // phase_eval / phase_sample read these two fields only
+        m.phase_kind = qi.phase_kind; m.g = qi.g;
+        LjPhaseResult o;
+        o.eval = phase_eval(m, ld3(qi.dir_in), ld3(qi.dir_out));
+        st3(o.sample, phase_sample(m, ld3(qi.dir_in), qi.rnd[0], qi.rnd[1]));
+        r[i] = o;
+    }
+}
+
+__global__ void __launch_bounds__(kQBlock) k_medium_queries(DScene sc, const LjMediumQuery *q, LjMediumResult *r, long long n) {
+    for (long long i = (long long)blockIdx.x * kQBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kQBlock) {
+        const LjMediumQuery qi = q[i];
+        const DMedium &m = sc.media[qi.medium_id];
+        f3 ss, sa;
+        get_sigmas(sc, m, ld3(qi.p), ss, sa);
+        LjMediumResult o;
+        st3(o.sigma_s, ss); st3(o.sigma_a, sa);
+        st3(o.majorant, get_majorant(m, ld3(qi.org), ld3(qi.dir), qi.tfar));
         r[i] = o;
     }
 }
@@ -296,6 +322,28 @@ int lj_frame_queries(lj_context *ctx, int64_t n, const LjFrameQuery *q, LjFrameR
         if (!ctx) throw LjError(LJ_ERR_INVALID_ARG, "lj_frame_queries: null context");
         run_queries(ctx, n, q, 1, r, 1, [&](const LjFrameQuery *qd, LjFrameResult *rd, hipStream_t s) {
             hipLaunchKernelGGL(ljd::k_frame_queries, dim3(grid_for(ctx, n)), dim3(ljd::kQBlock), 0, s, qd, rd, (long long)n);
+        });
+    });
+}
+
+int lj_phase_queries(lj_context *ctx, int64_t n, const LjPhaseQuery *q, LjPhaseResult *r) {
+    return lj::guard([&]() {
+        if (!ctx) throw LjError(LJ_ERR_INVALID_ARG, "lj_phase_queries: null context");
+        for (int64_t i = 0; i < n && q; i++)
+            if (q[i].phase_kind != LJ_PHASE_ISOTROPIC && q[i].phase_kind != LJ_PHASE_HG) throw LjError(LJ_ERR_INVALID_ARG, "lj_phase_queries: not a PhaseFunction alternative");
+        run_queries(ctx, n, q, 1, r, 1, [&](const LjPhaseQuery *qd, LjPhaseResult *rd, hipStream_t s) {
+            hipLaunchKernelGGL(ljd::k_phase_queries, dim3(grid_for(ctx, n)), dim3(ljd::kQBlock), 0, s, qd, rd, (long long)n);
+        });
+    });
+}
+
+int lj_medium_queries(lj_scene *scene, int64_t n, const LjMediumQuery *q, LjMediumResult *r) {
+    return lj::guard([&]() {
+        if (!scene) throw LjError(LJ_ERR_INVALID_ARG, "lj_medium_queries: null scene");
+        for (int64_t i = 0; i < n && q; i++)
+            if (q[i].medium_id < 0 || q[i].medium_id >= (int)scene->flat.media.size()) throw LjError(LJ_ERR_INVALID_ARG, "lj_medium_queries: medium_id out of range");
+        run_queries(scene->ctx, n, q, 1, r, 1, [&](const LjMediumQuery *qd, LjMediumResult *rd, hipStream_t s) {
+            hipLaunchKernelGGL(ljd::k_medium_queries, dim3(grid_for(scene->ctx, n)), dim3(ljd::kQBlock), 0, s, scene->dscene, qd, rd, (long long)n);
         });
     });
 }

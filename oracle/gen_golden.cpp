@@ -26,6 +26,7 @@
 #include "transform.h"
 #include "pcg.h"
 #include "3rdparty/pugixml.hpp"
+#include <algorithm>
 #include <cstdio>
 #include <map>
 #include <string>
@@ -70,6 +71,12 @@ struct J {
         else if (std::isinf(v)) fputs(v > 0 ? "\"inf\"" : "\"-inf\"", f);
         else fprintf(f, "%.17g", v);
     }
+    // short forms for the edge-case fixtures: a float input in 9 digits (read back through float32 it is the same float, and the sign of a
+    // zero survives a JSON reader), a reference output in 10 digits (far below any float bar)
+    void fnum(double v) { if (v == 0 && std::signbit(v)) { sep(); fputs("-0.0", f); } else if (std::isnan(v) || std::isinf(v)) num(v); else { sep(); fprintf(f, "%.9g", v); } }
+    void onum(double v) { if (std::isnan(v) || std::isinf(v)) num(v); else { sep(); fprintf(f, "%.10g", v); } }
+    void f3(const Vector3 &v) { fnum(v.x); fnum(v.y); fnum(v.z); }
+    void o3(const Vector3 &v) { onum(v.x); onum(v.y); onum(v.z); }
     void inum(long long v) { sep(); fprintf(f, "%lld", v); }
     void str(const std::string &s) { sep(); fprintf(f, "\"%s\"", s.c_str()); }
     void kv(const char *k, double v) { key(k); num(v); }
@@ -724,6 +731,338 @@ static void gen_media(const std::string &outdir, const fs::path &ref) {
     j.eobj();
 }
 
+// ---------------------------------------------------------------- edge cases of media and textures, on float inputs
+// Every input below is narrowed to float before the reference sees it, so that the float device code and the reference
+// work on identical numbers and their answers can be compared on discontinuities too (box faces, the 1e-3 threshold
+// of g, checker cell edges).  Both generators seed g_rng themselves and run after gen_media: no other fixture moves.
+static Real F(Real x) { return Real(float(x)); }
+static Vector3 F3(const Vector3 &v) { return Vector3{F(v.x), F(v.y), F(v.z)}; }
+static Real ulp_step(Real x, Real towards) { return Real(nextafterf(float(x), float(towards))); }
+
+static void gen_media_edges(const std::string &outdir) {
+    J j(outdir + "/media_edges.json");
+    j.obj();
+    j.ks("generator", "oracle/gen_golden.cpp gen_media_edges (init_pcg32(4242)): the reference's phase functions (phase_functions/*.inl), "
+                      "GridVolume lookup / intersect (volume.h) and HeterogeneousMedium queries (media/heterogeneous.inl) on float-narrowed edge inputs");
+    g_rng = init_pcg32(4242);
+    // ---- phase functions
+    const float e24 = ldexpf(1.0f, -24);
+    const float gs[] = {-2.0f /* isotropic */, 0.99f, -0.99f, 0.9f, -0.9f, 0.3f, -0.3f, 1e-3f, -1e-3f, 0.999e-3f, -0.999e-3f};
+    const Vector3 axes[6] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    j.ks("layouts", "phase case: [dir_in x3, dir_out x3, rnd x2, eval (== pdf), sample x3]; point: [p x3, sigma_s x3, sigma_a x3]; "
+                    "ray: [org x3, dir x3, tfar, hit] with majorant = hit ? the medium's majorant_hit : 0.  Inputs are floats written in 9 digits: "
+                    "read them through float32");
+    j.key("phase"); j.arr();
+    for (float gf : gs) {
+        const bool iso = gf == -2.0f;
+        const Real g = iso ? Real(0) : Real(gf);
+        PhaseFunction pf = iso ? PhaseFunction{IsotropicPhase{}} : PhaseFunction{HenyeyGreenstein{g}};
+        j.obj(); j.kv("g", g); j.ki("isotropic", iso ? 1 : 0);
+        j.key("cases"); j.arr();
+        for (int a = 0; a < 8; a++) {
+            const Vector3 din = a < 6 ? axes[a] : F3(rnd_dir());
+            std::vector<Vector2> rv;
+            const Real hi = Real(1.0f - e24), lo = Real(e24);
+            const Real v[4] = {0, lo, 0.5, hi};
+            if (a == 5) { for (Real x : v) for (Real y : v) rv.push_back(Vector2{x, y}); rv.push_back(Vector2{F(rnd()), F(rnd())}); }   // the singular branch of Frame: the whole rnd grid
+            else if (a < 5) { for (int k = 0; k < 3; k++) rv.push_back(Vector2{v[(k + a) % 4], v[(2 * k + a + 1) % 4]}); }
+            else for (int k = 0; k < 2; k++) rv.push_back(Vector2{F(rnd()), F(rnd())});
+            for (size_t k = 0; k < rv.size(); k++) {
+                Vector3 dout;
+                switch (k % 4) {
+                    case 0: dout = din; break;
+                    case 1: dout = -din; break;
+                    case 2: dout = a < 6 ? axes[(a + 2) % 6] : F3(normalize(cross(din, Vector3{0, 0, 1}))); break;
+                    default: dout = F3(rnd_dir()); break;
+                }
+                if (eval(pf, din, dout).x != pdf_sample_phase(pf, din, dout)) { fprintf(stderr, "eval != pdf\n"); exit(1); }
+                j.arr(); j.f3(din); j.f3(dout); j.fnum(rv[k].x); j.fnum(rv[k].y); j.onum(eval(pf, din, dout).x); j.o3(*sample_phase_function(pf, din, rv[k])); j.earr();
+            }
+        }
+        j.earr(); j.eobj();
+    }
+    j.earr();
+    // ---- synthetic grid volumes.  Boxes and scales are dyadic, so that slab distances of the axis-aligned and diagonal rays are exact.
+    struct VolSpec { const char *name; int rx, ry, rz; bool mono; Vector3 lo, hi; Real scale; };
+    const VolSpec specs[] = {
+        {"rgb_3x4x5", 3, 4, 5, false, Vector3{-0.5, 0.25, 1.0}, Vector3{1.5, 1.0, 3.0}, 2.5},
+        {"mono_2x2x2", 2, 2, 2, true, Vector3{-1.0, -1.0, -1.0}, Vector3{1.0, 2.0, 3.0}, 0.75},
+        {"rgb_1x3x4", 1, 3, 4, false, Vector3{0.125, -2.0, 0.5}, Vector3{0.625, -1.0, 4.5}, 3},
+    };
+    j.key("note_rays"); j.str("rays whose direction has a zero component along an axis on whose face plane the origin lies divide 0 by 0 in the slab test; "
+                              "their majorant is what the reference's comparisons then give and is recorded as such");
+    j.key("volumes"); j.arr();
+    long long n_pts = 0, n_in = 0, n_rays = 0, n_hit = 0;
+    for (const VolSpec &vs : specs) {
+        GridVolume<Spectrum> grid;
+        grid.resolution = Vector3i{vs.rx, vs.ry, vs.rz}; grid.p_min = vs.lo; grid.p_max = vs.hi; grid.scale = vs.scale;
+        grid.max_data = Vector3{0, 0, 0};
+        for (int i = 0; i < vs.rx * vs.ry * vs.rz; i++) {
+            Vector3 d = vs.mono ? Vector3{1, 1, 1} * F(Real(0.125) + rnd()) : Vector3{F(rnd()), F(Real(0.25) + rnd()), F(Real(0.5) * rnd())};
+            grid.data.push_back(d); grid.max_data = max(grid.max_data, d);
+        }
+        const Vector3 lo = vs.lo, hi = vs.hi, ext = hi - lo, ctr = (lo + hi) / Real(2);
+        j.obj(); j.ks("name", vs.name);
+        j.key("resolution"); j.arr(); j.inum(vs.rx); j.inum(vs.ry); j.inum(vs.rz); j.earr();
+        j.ki("mono", vs.mono ? 1 : 0); j.kv3("p_min", lo); j.kv3("p_max", hi); j.kv("scale", vs.scale); j.kv3("max_data", grid.max_data);
+        j.key("data"); j.arr(); for (auto &d : grid.data) j.f3(d); j.earr();
+        // points
+        std::vector<Vector3> pts;
+        auto at = [&](Real fx, Real fy, Real fz) { return F3(Vector3{lo.x + ext.x * fx, lo.y + ext.y * fy, lo.z + ext.z * fz}); };
+        for (int z = 0; z < vs.rz; z++) for (int y = 0; y < vs.ry; y++) for (int x = 0; x < vs.rx; x++)   // grid nodes
+            pts.push_back(at(vs.rx > 1 ? Real(x) / (vs.rx - 1) : Real(0.5), vs.ry > 1 ? Real(y) / (vs.ry - 1) : Real(0.5), vs.rz > 1 ? Real(z) / (vs.rz - 1) : Real(0.5)));
+        const Real mid[3] = {0.37, 0.61, 0.43};
+        for (int c = 0; c < 27; c++) {   // faces, edges and corners: each coordinate exactly p_min, exactly p_max, or inside
+            const int k[3] = {c % 3, (c / 3) % 3, c / 9};
+            if (k[0] == 1 && k[1] == 1 && k[2] == 1) continue;
+            Vector3 p = at(mid[0], mid[1], mid[2]);
+            for (int a = 0; a < 3; a++) if (k[a] != 1) p[a] = k[a] == 0 ? lo[a] : hi[a];
+            pts.push_back(p);
+        }
+        for (int a = 0; a < 3; a++) for (int side = 0; side < 2; side++) for (int dirn = 0; dirn < 2; dirn++) {   // one float ulp inside / outside each face
+            Vector3 p = at(mid[0], mid[1], mid[2]);
+            const Real face = side == 0 ? lo[a] : hi[a];
+            p[a] = ulp_step(face, dirn == 0 ? ctr[a] : face + (face - ctr[a]));
+            pts.push_back(p);
+        }
+        for (int z = 0; z < std::max(vs.rz - 1, 1); z += 3) for (int y = 0; y < std::max(vs.ry - 1, 1); y += 2) for (int x = 0; x < std::max(vs.rx - 1, 1); x++)   // cell centres
+            pts.push_back(at((x + Real(0.5)) / std::max(vs.rx - 1, 1), (y + Real(0.5)) / std::max(vs.ry - 1, 1), (z + Real(0.5)) / std::max(vs.rz - 1, 1)));
+        for (int i = 0; i < 6; i++) pts.push_back(at(rnd(), rnd(), rnd()));
+        for (int i = 0; i < 20; i++) pts.push_back(at(2 * rnd() - Real(0.5), 2 * rnd() - Real(0.5), 2 * rnd() - Real(0.5)));
+        // rays
+        struct R { Vector3 org, dir; Real tfar; };
+        std::vector<R> rays;
+        const Real inf = infinity<Real>();
+        auto ray = [&](Vector3 o, Vector3 d, Real tf) { rays.push_back(R{F3(o), F3(d), F(tf)}); };
+        for (int a = 0; a < 3; a++) for (int sgn = -1; sgn <= 1; sgn += 2) {
+            Vector3 ax{0, 0, 0}; ax[a] = sgn;
+            const Vector3 o = ctr - ax * (Real(1.5) * ext[a]);   // outside, on the axis through the centre: the box spans t in [ext, 2 ext]
+            ray(o, ax, inf); ray(o, -ax, inf);
+            ray(o, ax, Real(0.5) * ext[a]); ray(o, ax, ext[a]); ray(o, ax, Real(1.5) * ext[a]); ray(o, ax, 0);
+            ray(ctr, ax, inf); ray(ctr, ax, 0); ray(ctr, ax, Real(0.25) * ext[a]);
+            Vector3 f = at(mid[0], mid[1], mid[2]); f[a] = sgn < 0 ? lo[a] : hi[a];   // on a face
+            ray(f, ax, inf); ray(f, -ax, inf); ray(f, ax, 0);
+            if (const int b = (a + 1) % 3; true) for (Real zero : {Real(0.0), Real(-0.0)}) if (zero == 0 && (a == 0 || !std::signbit(zero))) {   // parallel to the faces of axis a, along axis b
+                Vector3 d{zero, zero, zero}; d[b] = 1;
+                Vector3 o2 = ctr; o2[b] = lo[b] - 1;
+                ray(o2, d, inf);                                                     // inside the slab
+                o2[a] = sgn < 0 ? lo[a] - Real(0.5) : hi[a] + Real(0.5); ray(o2, d, inf);   // outside it
+                o2[a] = sgn < 0 ? lo[a] : hi[a]; ray(o2, d, inf);                    // in the face plane: 0 / 0
+                ray(f, d, inf); ray(f, -d, Real(0.5));
+            }
+        }
+        for (int c = 0; c < 8; c++) {   // diagonals: from the centre, through a corner from outside, grazing an edge
+            const Vector3 sg{c & 1 ? 1.0 : -1.0, c & 2 ? 1.0 : -1.0, c & 4 ? 1.0 : -1.0};
+            const Vector3 d = sg / sqrt(Real(3));
+            Vector3 corner{sg.x < 0 ? hi.x : lo.x, sg.y < 0 ? hi.y : lo.y, sg.z < 0 ? hi.z : lo.z};   // the corner the ray enters through
+            ray(ctr, d, inf); ray(corner - sg, d, inf); ray(corner - sg, d, 1); ray(corner - sg, -d, inf);
+            const Vector3 dxy{sg.x, -sg.y, Real(0)}, d2 = dxy / sqrt(Real(2));
+            Vector3 edge{sg.x < 0 ? hi.x : lo.x, sg.y < 0 ? hi.y : lo.y, ctr.z};   // touches this edge of the box and nothing else
+            ray(edge - dxy, d2, inf);
+            ray(edge - dxy - Vector3{Real(0), sg.y * Real(0.25), Real(0)}, d2, inf);   // moved outwards: passes it by
+            ray(edge - dxy + Vector3{Real(0), sg.y * Real(0.25), Real(0)}, d2, inf);   // moved inwards: cuts the corner
+        }
+        for (int i = 0; i < 12; i++) {
+            Vector3 o = at(rnd() * 3 - 1, rnd() * 3 - 1, rnd() * 3 - 1);
+            ray(o, rnd_dir(), i % 3 == 0 ? ext.x * rnd() : inf);
+        }
+        // the two media: grid density under a constant albedo, grid albedo under a constant density
+        j.key("media"); j.arr();
+        for (int mi = 0; mi < 2; mi++) {
+            HeterogeneousMedium hm;
+            hm.phase_function = IsotropicPhase{};
+            const Vector3 cst = mi == 0 ? Vector3{0.25, 0.5, 0.875} : Vector3{1.5, 2.0, 0.5};
+            if (mi == 0) { hm.density = grid; hm.albedo = ConstantVolume<Spectrum>{cst}; }
+            else { hm.albedo = grid; hm.density = ConstantVolume<Spectrum>{cst}; }
+            Medium m = hm;
+            const Spectrum mj_hit = get_majorant(m, Ray{ctr, Vector3{1.0, 0.0, 0.0}, Real(0), infinity<Real>()});
+            j.obj(); j.ks("grid", mi == 0 ? "density" : "albedo"); j.kv3("constant", cst); j.kv3("majorant_hit", mj_hit);
+            j.key("points"); j.arr();
+            for (size_t pi = 0; pi < pts.size(); pi += (mi == 0 ? 1 : 2)) {   // (the albedo grid runs the same lookup: every other point)
+                const Vector3 &p = pts[pi];
+                j.arr(); j.f3(p); j.o3(get_sigma_s(m, p)); j.o3(get_sigma_a(m, p)); j.earr();
+                if (mi == 0) { n_pts++; n_in += (p.x >= lo.x && p.x <= hi.x && p.y >= lo.y && p.y <= hi.y && p.z >= lo.z && p.z <= hi.z); }
+            }
+            j.earr();
+            j.key("rays"); j.arr();
+            for (size_t i = 0; i < rays.size(); i += (mi == 0 ? 1 : 9)) {   // (a constant density is hit by every ray: a few suffice)
+                const R &r = rays[i];
+                Spectrum mj = get_majorant(m, Ray{r.org, r.dir, Real(0), r.tfar});
+                const bool hit = mj.x > 0;
+                if (hit ? !(mj.x == mj_hit.x && mj.y == mj_hit.y && mj.z == mj_hit.z) : (mj.y != 0 || mj.z != 0)) { fprintf(stderr, "majorant is neither 0 nor the maximum\n"); exit(1); }
+                j.arr(); j.f3(r.org); j.f3(r.dir); j.fnum(r.tfar); j.inum(hit ? 1 : 0); j.earr();
+                if (mi == 0) { n_rays++; n_hit += mj.x > 0; }
+            }
+            j.earr();
+            j.eobj();
+        }
+        j.earr();
+        j.eobj();
+    }
+    {   // a grid whose x = 0 plane is infinite, looked up on and next to the face x = p_max only.  On that face x0 is the last node and the
+        // weight of its neighbour x1 is exactly 0: a neighbour index that wraps to node 0 instead of staying on the last node shows there
+        // (0 * inf), and nowhere else.
+        GridVolume<Spectrum> grid;
+        grid.resolution = Vector3i{3, 2, 2}; grid.p_min = Vector3{-1.0, 0.0, 0.5}; grid.p_max = Vector3{1.0, 0.5, 1.5}; grid.scale = 1.5;
+        const Real inf = infinity<Real>();
+        for (int i = 0; i < 12; i++) grid.data.push_back(i % 3 == 0 ? Vector3{inf, inf, inf} : Vector3{F(rnd()), F(rnd()), F(rnd())});
+        grid.max_data = Vector3{inf, inf, inf};
+        const Vector3 lo = grid.p_min, hi = grid.p_max, ext = hi - lo;
+        j.obj(); j.ks("name", "rgb_3x2x2_inf_plane");
+        j.key("resolution"); j.arr(); j.inum(3); j.inum(2); j.inum(2); j.earr();
+        j.ki("mono", 0); j.kv3("p_min", lo); j.kv3("p_max", hi); j.kv("scale", grid.scale); j.kv3("max_data", grid.max_data);
+        j.key("data"); j.arr(); for (auto &d : grid.data) j.f3(d); j.earr();
+        HeterogeneousMedium hm;
+        hm.phase_function = IsotropicPhase{};
+        const Vector3 cst{0.25, 0.5, 0.875};
+        hm.density = grid; hm.albedo = ConstantVolume<Spectrum>{cst};
+        Medium m = hm;
+        j.key("media"); j.arr(); j.obj(); j.ks("grid", "density"); j.kv3("constant", cst); j.kv3("majorant_hit", grid.scale * grid.max_data);
+        j.key("points"); j.arr();
+        for (Real fy : {Real(0), Real(0.37), Real(1)}) for (Real fz : {Real(0), Real(0.61), Real(1)}) for (int in = 0; in < 2; in++) {
+            const Vector3 p = F3(Vector3{in ? ulp_step(hi.x, lo.x) : hi.x, lo.y + ext.y * fy, lo.z + ext.z * fz});
+            j.arr(); j.f3(p); j.o3(get_sigma_s(m, p)); j.o3(get_sigma_a(m, p)); j.earr();
+        }
+        j.earr();
+        j.key("rays"); j.arr(); j.earr();
+        j.eobj(); j.earr();
+        j.eobj();
+    }
+    j.earr();
+    j.eobj();
+    fprintf(stderr, "media_edges: %lld points, %lld inside; %lld rays, %lld hit\n", n_pts, n_in, n_rays, n_hit);
+}
+
+// image pixels: row y draws from init_pcg32(y, seed), x-major then channel, value = (next_pcg32 >> 20) / 4096 (a float, exactly)
+static Real px_value(pcg32_state &s) { return Real(next_pcg32(s) >> 20) / Real(4096); }
+static Image3 synth_image3(int w, int h, uint64_t seed) {
+    Image3 img(w, h);
+    for (int y = 0; y < h; y++) { pcg32_state s = init_pcg32(y, seed); for (int x = 0; x < w; x++) { Real r = px_value(s), g = px_value(s), b = px_value(s); img(x, y) = Vector3{r, g, b}; } }
+    return img;
+}
+static Image1 synth_image1(int w, int h, uint64_t seed) {
+    Image1 img(w, h);
+    for (int y = 0; y < h; y++) { pcg32_state s = init_pcg32(y, seed); for (int x = 0; x < w; x++) img(x, y) = px_value(s); }
+    return img;
+}
+
+static void gen_textures(const std::string &outdir) {
+    J j(outdir + "/textures.json");
+    j.obj();
+    j.ks("generator", "oracle/gen_golden.cpp gen_textures (init_pcg32(777)): eval(texture, uv, footprint, pool) (texture.h:123-154, mipmap.h:25-89) of in-memory "
+                      "images put through make_image_spectrum_texture / make_image_float_texture, and of checkerboards");
+    j.ks("pixel_formula", "row y of an image draws from init_pcg32(stream = y, seed): for x = 0..w-1, for each channel, pixel = (next_pcg32 >> 20) / 4096; "
+                          "`pixels_k` holds the integers (row-major, channels interleaved) of the images up to 37x23, `sum_k` their sum for every image");
+    j.ks("note_levels", "make_mipmap reads outside a parent level that is 1 texel wide or high (mipmap.h:38-42): for 37x23 (levels 37x23 18x11 9x5 4x2 2x1 1x1 1x1) only "
+                        "footprints whose level is below 3.9 are recorded, so both blended levels (at most 2x1, halved from 4x2) have parents of at least 2x2; "
+                        "every level of the square images and of 300x200 (down to 2x1, halved from 4x3) is defined");
+    j.ks("lookup_layout", "[uscale, vscale, uoffset, voffset, u, v, footprint, value...] (3 values for the spectrum pool, 1 for the float pool); footprint is a float written in 9 digits (read it through float32), values have 10 digits, random uv are odd multiples of 2^-13; "
+                          "centres: [level, ix, iy, footprint, value...] — uv = ((ix + 0.5) / w, (iy + 0.5) / h) of mip level `level` (w x h, halved and floored per level), unit scale");
+    g_rng = init_pcg32(777);
+    TexturePool pool;
+    struct ImgSpec { int w, h, ch; uint64_t seed; bool store; Real level_cap; };
+    const ImgSpec imgs[] = {
+        {1, 1, 3, 101, true, 1e9}, {2, 2, 3, 102, true, 1e9}, {4, 4, 3, 103, true, 1e9}, {64, 64, 3, 104, false, 1e9}, {37, 23, 3, 105, true, 3.9}, {300, 200, 3, 106, false, 1e9},
+        {37, 23, 1, 202, true, 3.9}, {64, 64, 1, 203, false, 1e9},
+    };
+    const Real scales[][4] = {{3, 3, 0, 0}, {0.5, 0.5, 0, 0}, {3, 0.5, 0.25, 0.75}, {1, 3, -0.5, 0.125}, {0.5, 1, 10.25, -3.5}};
+    long long n_lookups = 0;
+    j.key("images"); j.arr();
+    int n3 = 0, n1 = 0;
+    for (const ImgSpec &is : imgs) {
+        const bool spec = is.ch == 3;
+        const std::string name = "img" + std::to_string(is.seed);
+        Image3 i3; Image1 i1;
+        int id, levels;
+        if (spec) { i3 = synth_image3(is.w, is.h, is.seed); id = make_image_spectrum_texture(name, i3, pool).texture_id; levels = (int)pool.image3s[id].images.size(); n3++; }
+        else { i1 = synth_image1(is.w, is.h, is.seed); id = make_image_float_texture(name, i1, pool).texture_id; levels = (int)pool.image1s[id].images.size(); n1++; }
+        const int W = is.w, H = is.h, size = std::max(W, H);
+        j.obj(); j.ki("width", W); j.ki("height", H); j.ki("channels", is.ch); j.ki("texture_id", id); j.ks("seed", std::to_string(is.seed)); j.ki("levels", levels);
+        long long sum = 0;
+        if (is.store) { j.key("pixels_k"); j.arr(); }
+        for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) for (int c = 0; c < is.ch; c++) {
+            const long long k = (long long)llround((spec ? i3(x, y)[c] : i1(x, y)) * 4096);
+            sum += k; if (is.store) j.inum(k);
+        }
+        if (is.store) j.earr();
+        j.ki("sum_k", sum);
+        auto level_of = [&](Real us, Real vs, Real fp) { return log2(max(Real(size) * max(us, vs) * fp, Real(1e-8f))); };
+        auto val = [&](Real x) { j.sep(); fprintf(j.f, "%.10g", x); };
+        auto rq = [&]() { return (floor(rnd() * 4096) + Real(0.5)) / 4096; };   // a random coordinate that prints short and exactly
+        auto look = [&](Real us, Real vs, Real uo, Real vo, Real u, Real v, Real fp) {
+            fp = F(fp);
+            if (level_of(us, vs, fp) >= is.level_cap) return;
+            j.arr(); j.num(us); j.num(vs); j.num(uo); j.num(vo); j.num(u); j.num(v); j.fnum(fp);
+            if (spec) { Vector3 c = eval(Texture<Spectrum>{ImageTexture<Spectrum>{id, us, vs, uo, vo}}, Vector2{u, v}, fp, pool); val(c.x); val(c.y); val(c.z); }
+            else val(eval(Texture<Real>{ImageTexture<Real>{id, us, vs, uo, vo}}, Vector2{u, v}, fp, pool));
+            j.earr(); n_lookups++;
+        };
+        // uv set
+        std::vector<Vector2> uvs;
+        auto pick = [](int n) { std::vector<int> v{0, n / 2, n - 1}, o; for (int x : v) if (x >= 0 && x < n && std::find(o.begin(), o.end(), x) == o.end()) o.push_back(x); return o; };
+        for (int y : pick(H)) for (int x : pick(W)) uvs.push_back(Vector2{(x + Real(0.5)) / W, (y + Real(0.5)) / H});           // texel centres
+        { const int cx[4] = {0, 1, W - 1, W}, cy[4] = {0, H, 1, H - 1};
+          for (int a = 0; a < 4; a++) for (int b = a; b < 4; b += 3) uvs.push_back(Vector2{Real(cx[a]) / W, Real(cy[b]) / H}); }   // texel corners, 0 and 1
+        const Real sp[] = {0, 1, 1 - ldexp(Real(1), -53), Real(0.25) / W, Real(0.4) / H, -0.3, -1e-20, 37.25, -37.25, 1e4 + 0.3, -1e4 - 0.3};
+        const int nsp = sizeof(sp) / sizeof(sp[0]);
+        for (int a = 0; a < nsp; a++) { uvs.push_back(Vector2{sp[a], sp[(a + 3) % nsp]}); if (a % 2) uvs.push_back(Vector2{sp[a], rq()}); else uvs.push_back(Vector2{rq(), sp[a]}); }
+        for (int a = 0; a < 4; a++) uvs.push_back(Vector2{rq(), rq()});
+        j.key("lookups"); j.arr();
+        const Real frac_fp = pow(Real(2), Real(levels > 1 ? 0.37 : -0.5)) / size;
+        for (size_t a = 0; a < uvs.size(); a++) { look(1, 1, 0, 0, uvs[a].x, uvs[a].y, 0); if (a % 3 == 0) look(1, 1, 0, 0, uvs[a].x, uvs[a].y, frac_fp); }
+        // footprints: below level 0, fractional levels, the top level exactly, beyond the top
+        std::vector<Real> fps{Real(0.25) / size, Real(1) / size, pow(Real(2), levels - 1) / size, pow(Real(2), levels - 1 + Real(0.5)) / size, pow(Real(2), levels + 1) / size, 1e-12, 1e3};
+        for (int l = 0; l + 1 < levels; l++) { fps.push_back(pow(Real(2), l + Real(0.63)) / size); fps.push_back(pow(Real(2), l + Real(0.999)) / size); fps.push_back(pow(Real(2), l + Real(0.001)) / size); }
+        for (size_t a = 0; a < fps.size(); a++) { const Vector2 &uv = uvs[(a * 7) % uvs.size()]; if (a % 2) look(1, 1, 0, 0, uv.x, uv.y, fps[a]); else look(1, 1, 0, 0, rq(), rq(), fps[a]); }
+        // scales and offsets
+        for (auto &sc : scales) for (int a = 0; a < 4; a++) {
+            const Vector2 uv = a < 3 ? uvs[(a * 11 + 3) % uvs.size()] : Vector2{rq() * 4 - 2, rq() * 4 - 2};
+            look(sc[0], sc[1], sc[2], sc[3], uv.x, uv.y, 0); look(sc[0], sc[1], sc[2], sc[3], uv.x, uv.y, frac_fp * Real(1.7));
+            if (a < 1) look(sc[0], sc[1], sc[2], sc[3], uv.x, uv.y, pow(Real(2), levels - 1) / size / max(sc[0], sc[1]));
+        }
+        j.earr();
+        // the mip chain through lookups: integer level l at the centres of that level's texels
+        j.key("centres"); j.arr();
+        for (int l = 0; l < levels; l++) {
+            const Real fp = F(pow(Real(2), l) / size);
+            if (level_of(1, 1, fp) >= is.level_cap) continue;
+            const int wl = spec ? pool.image3s[id].images[l].width : pool.image1s[id].images[l].width, hl = spec ? pool.image3s[id].images[l].height : pool.image1s[id].images[l].height;
+            for (int y : pick(hl)) for (int x : pick(wl)) {
+                const Real u = (x + Real(0.5)) / wl, v = (y + Real(0.5)) / hl;
+                j.arr(); j.inum(l); j.inum(x); j.inum(y); j.fnum(fp);
+                if (spec) { Vector3 c = eval(Texture<Spectrum>{ImageTexture<Spectrum>{id, 1, 1, 0, 0}}, Vector2{u, v}, fp, pool); val(c.x); val(c.y); val(c.z); }
+                else val(eval(Texture<Real>{ImageTexture<Real>{id, 1, 1, 0, 0}}, Vector2{u, v}, fp, pool));
+                j.earr(); n_lookups++;
+            }
+        }
+        j.earr();
+        j.eobj();
+    }
+    j.earr();
+    // ---- checkerboards: [u, v, value...]
+    j.key("checkerboards"); j.arr();
+    const Real cfg[][4] = {{1, 1, 0, 0}, {2, 2, 0, 0}, {4, 3, 0.125, 0.25}, {0.5, 0.5, 0, 0}, {3, 1, -0.25, 0.5}};
+    const Real cu[] = {0, 0.25, 0.5, 0.75, 1, -0.25, -0.5, -1, 0.125, -37.25, 1 - ldexp(Real(1), -53), -1e-20, 1e4 + 0.3};
+    const Real cv[] = {0, 0.5, -0.5, 0.3, 2.25};
+    for (int spec = 1; spec >= 0; spec--) for (auto &c : cfg) {
+        if (!spec && c[0] != 4 && c[0] != 1) continue;   // (the float checkerboard is the same code: two of the five)
+        const Vector3 c0{0.75, 0.25, 0.5}, c1{0.125, 1.0, 0.0625};
+        j.obj(); j.ki("spectrum", spec); j.kv("uscale", c[0]); j.kv("vscale", c[1]); j.kv("uoffset", c[2]); j.kv("voffset", c[3]);
+        if (spec) { j.kv3("color0", c0); j.kv3("color1", c1); } else { j.kv("color0", c0.x); j.kv("color1", c1.x); }
+        j.key("lookups"); j.arr();
+        for (Real u : cu) for (Real v : cv) {
+            j.arr(); j.num(u); j.num(v);
+            if (spec) { Vector3 r = eval(Texture<Spectrum>{make_checkerboard_spectrum_texture(c0, c1, c[0], c[1], c[2], c[3])}, Vector2{u, v}, Real(0), pool); j.num(r.x); j.num(r.y); j.num(r.z); }
+            else j.num(eval(Texture<Real>{CheckerboardTexture<Real>{c0.x, c1.x, c[0], c[1], c[2], c[3]}}, Vector2{u, v}, Real(0), pool));
+            j.earr(); n_lookups++;
+        }
+        j.earr(); j.eobj();
+    }
+    j.earr();
+    j.eobj();
+    fprintf(stderr, "textures: %d + %d images, %lld lookups\n", n3, n1, n_lookups);
+}
+
 int main(int argc, char **argv) {
     if (argc < 3) { fprintf(stderr, "usage: gen_golden <reference_root> <outdir>\n"); return 1; }
     fs::path ref = fs::absolute(argv[1]); std::string out = fs::absolute(argv[2]).string();
@@ -734,6 +1073,8 @@ int main(int argc, char **argv) {
     gen_scene(out, "disney_bsdf", ref / "scenes/disney_bsdf_test/disney_bsdf.xml", false);
     gen_scene(out, "sponza", ref / "scenes/sponza/sponza.xml", false);
     gen_media(out, ref);
+    gen_media_edges(out);
+    gen_textures(out);
     // _exit: static destructors of the leaked fake Scenes must never run (they would call into Embree).
     fflush(nullptr); _exit(0);
 }

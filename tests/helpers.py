@@ -378,6 +378,19 @@ class TwinQueries:
         self.lib.twin_frame_queries(C.c_int64(len(q)), q.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p))
         return r
 
+    def phase(self, q):
+        q = np.ascontiguousarray(q, lj.PHASE_QUERY).reshape(-1)
+        r = np.zeros(len(q), lj.PHASE_RESULT)
+        self.lib.twin_phase_queries(C.c_int64(len(q)), q.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p))
+        return r
+
+    def medium(self, q):
+        q = np.ascontiguousarray(q, lj.MEDIUM_QUERY).reshape(-1)
+        r = np.zeros(len(q), lj.MEDIUM_RESULT)
+        if self.lib.twin_medium_queries(self.tw.h, C.c_int64(len(q)), q.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p)) != 0:
+            raise lj.LajollaError(_abi.LJ_ERR_INVALID_ARG, "twin_medium_queries: medium_id out of range")
+        return r
+
 
 class GpuQueries:
     """The same interface through the C ABI of liblajolla_hip.so on cuda:0 (queries.hip)."""
@@ -426,6 +439,12 @@ class GpuQueries:
 
     def frame(self, q):
         return lj.frame_queries(self.ctx, q)
+
+    def phase(self, q):
+        return lj.phase_queries(self.ctx, q)
+
+    def medium(self, q):
+        return lj.medium_queries(self.scene, q)
 
 
 def with_materials(hs, material_dicts):

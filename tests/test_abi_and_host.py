@@ -33,7 +33,8 @@ def test_struct_sizes_match_the_header(tmp_path):
     """Compile a tiny C program against the header and compare sizeof() with the ctypes mirror."""
     names = ["LjTexture", "LjMaterial", "LjShape", "LjLight", "LjImage", "LjCamera", "LjVolume", "LjMedium", "LjRenderOptions", "LjSceneDesc", "LjRenderArgs",
              "LjRay", "LjHit", "LjStats", "LjSceneInfo", "LjVertex", "LjBsdfQuery", "LjBsdfResult", "LjLightQuery", "LjLightResult", "LjHitQuery",
-             "LjHitResult", "LjPrimaryQuery", "LjPrimaryResult", "LjFilterQuery", "LjTextureQuery", "LjFrameQuery", "LjFrameResult"]
+             "LjHitResult", "LjPrimaryQuery", "LjPrimaryResult", "LjFilterQuery", "LjTextureQuery", "LjFrameQuery", "LjFrameResult",
+             "LjPhaseQuery", "LjPhaseResult", "LjMediumQuery", "LjMediumResult"]
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include "lajolla_hip.h"\nint main(){' + "".join(f'printf("%zu\\n", sizeof({n}));' for n in names) + "return 0;}")
     exe = tmp_path / "sz"
@@ -48,6 +49,14 @@ def test_device_entry_points_fail_loudly_without_a_gpu():
     with pytest.raises(lj.LajollaError) as e:
         lj.Context(0)
     assert e.value.code == _abi.LJ_ERR_DEVICE and "no CPU path" in str(e.value)
+    # the media queries answer on a device only: without a context or an uploaded scene there is nothing that could, and they say so
+    lib = lj.load_library()
+    pq, pr = np.zeros(1, lj.PHASE_QUERY), np.zeros(1, lj.PHASE_RESULT)
+    assert lib.lj_phase_queries(None, 1, pq.ctypes.data_as(C.c_void_p), pr.ctypes.data_as(C.c_void_p)) == _abi.LJ_ERR_INVALID_ARG
+    assert b"lj_phase_queries" in lib.lj_last_error() and not pr["eval"].any()
+    mq, mr = np.zeros(1, lj.MEDIUM_QUERY), np.zeros(1, lj.MEDIUM_RESULT)
+    assert lib.lj_medium_queries(None, 1, mq.ctypes.data_as(C.c_void_p), mr.ctypes.data_as(C.c_void_p)) == _abi.LJ_ERR_INVALID_ARG
+    assert b"lj_medium_queries" in lib.lj_last_error() and not mr["majorant"].any()
 
 
 def test_null_arguments_are_rejected():
@@ -57,6 +66,8 @@ def test_null_arguments_are_rejected():
     assert lib.lj_render(None, None, None) == _abi.LJ_ERR_INVALID_ARG
     assert lib.lj_get_stats(None, None) == _abi.LJ_ERR_INVALID_ARG
     assert b"null" in lib.lj_last_error()
+    assert lib.lj_phase_queries(None, 0, None, None) == _abi.LJ_ERR_INVALID_ARG and b"null" in lib.lj_last_error()
+    assert lib.lj_medium_queries(None, 0, None, None) == _abi.LJ_ERR_INVALID_ARG and b"null" in lib.lj_last_error()
 
 
 @pytest.mark.parametrize("name", ["cbox", "veach_mi", "disney_bsdf", "sponza"])

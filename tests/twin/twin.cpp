@@ -289,6 +289,27 @@ void twin_frame_queries(int64_t n, const LjFrameQuery *q, LjFrameResult *r) {
         st3(r[i].x, f.x); st3(r[i].y, f.y); st3(r[i].to_local, to_local(f, v)); st3(r[i].to_world, to_world(f, v));
     }
 }
+void twin_phase_queries(int64_t n, const LjPhaseQuery *q, LjPhaseResult *r) {
+    for (int64_t i = 0; i < n; i++) {
+        DMedium m{};
+        m.phase_kind = q[i].phase_kind; m.g = q[i].g;
+        r[i].eval = phase_eval(m, ld3(q[i].dir_in), ld3(q[i].dir_out));
+        st3(r[i].sample, phase_sample(m, ld3(q[i].dir_in), q[i].rnd[0], q[i].rnd[1]));
+    }
+}
+// -1: a medium_id outside the scene's media (lj_medium_queries: LJ_ERR_INVALID_ARG)
+int twin_medium_queries(void *tv, int64_t n, const LjMediumQuery *q, LjMediumResult *r) {
+    const DScene &sc = ((Twin *)tv)->view;
+    for (int64_t i = 0; i < n; i++) if (q[i].medium_id < 0 || q[i].medium_id >= sc.n_media) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        const DMedium &m = sc.media[q[i].medium_id];
+        f3 ss, sa;
+        get_sigmas(sc, m, ld3(q[i].p), ss, sa);
+        st3(r[i].sigma_s, ss); st3(r[i].sigma_a, sa);
+        st3(r[i].majorant, get_majorant(m, ld3(q[i].org), ld3(q[i].dir), q[i].tfar));
+    }
+    return 0;
+}
 int twin_shade_variant(void *tv) {
     Twin *t = (Twin *)tv;
     uint32_t kinds = 0; bool textured = false, sphere_lights = false;
