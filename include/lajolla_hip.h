@@ -242,6 +242,34 @@ int lj_camera_look_at(const double origin[3], const double target[3], const doub
  * else is rebuilt.  Film size and filter may change.  Later lj_render* / lj_*_queries calls see the new camera. */
 int lj_scene_set_camera(lj_scene *scene, const LjCamera *camera);
 
+/* ---- moving geometry of an uploaded scene
+ * The uploaded scene with its vertices moved: re-derives everything lj_scene_upload derives from positions, normals and sphere
+ * position / radius — by the same code — and refits the boxes of the BVH4, the BVH8 and the tiny-scene leaf table on the device.
+ * The trees' topology, leaf order, mip pyramids, environment-map tables, materials, media, camera and kernel plan are kept.
+ *
+ * desc is the description that was uploaded, in which only `positions`, `normals` and each sphere's `position` / `radius` may differ.
+ * The call reads again what the geometry and light sections of the upload read — shapes, positions, normals, uvs, indices and lights —
+ * and IGNORES camera, options, materials, images and media.  Checked, LJ_ERR_INVALID_ARG otherwise: n_shapes, n_vertices, n_triangles,
+ * n_lights; per shape kind, vertex and triangle range, has_normals / has_uvs, material, light and medium ids; per light kind and
+ * shape_id; the index and uv arrays (by a 64-bit hash kept at upload); finite positions, normals, sphere centres and radii; a scene
+ * extent inside the BVH8 grid's exponent range.  Every check runs on the host before the first device write: a refused call leaves the
+ * scene exactly as it was.
+ *
+ * Closest hits are the minimum of (t, global primitive id) over everything a ray tests, so they do not depend on the tree: hits and
+ * per-sample radiance after an update are bit-identical to those of a fresh lj_scene_upload of the same description.  What a refit costs
+ * is tree quality (a tree built for the old positions; leaves that spatial splits had clipped get their primitives' whole boxes), i.e.
+ * render time — never a hit.
+ *
+ * Blocking, ordered on the context's stream: later lj_render*, lj_render_views*, lj_intersect / lj_occluded and lj_*_queries calls see the
+ * new geometry, lj_scene_info the new bounds and shadow_epsilon.  lj_get_stats after the call: render_ms = the update's device time,
+ * generate_ms = the host time of the re-derivation.  Device groups: apply the update to each lj_group_scene_member. */
+int lj_scene_update_geometry(lj_scene *scene, const LjSceneDesc *desc);
+
+/* Readback of an acceleration structure as it stands on the device, for tests: which = 0 the BVH4 (128-byte DNode4 records), 1 the BVH8
+ * (80-byte DNode8 records, packed whatever their stride on the device), 2 a tiny scene's leaf table (32-byte DScanLeaf records; none for
+ * other scenes).  *bytes = the size of the structure; out_host may be null to ask for it, else capacity_bytes must hold it. */
+int lj_scene_read_bvh(const lj_scene *scene, int32_t which, void *out_host, int64_t capacity_bytes, int64_t *bytes);
+
 /* n_views renders of the scene in one pass: rgb[n_views][h][w][3].  Every view must have the scene camera's width, height, filter_kind,
  * filter_param and medium_id (else LJ_ERR_INVALID_ARG); cam_to_world and sample_to_cam are per view.  View v is bit-identical to
  * lj_render of the same scene uploaded with views[v] and the same args: the batch is rendered as one frame of n_views * h rows whose

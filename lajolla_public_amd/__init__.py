@@ -91,6 +91,17 @@ class HostScene:
         n = self.desc.n_vertices
         return np.ctypeslib.as_array(self.desc.uvs, shape=(n, 2)).copy() if n else np.zeros((0, 2))
 
+    def positions_view(self):
+        """The description's own position array, (n_vertices, 3) float64: writable and not a copy — what is written here is what
+        Scene(ctx, hs) and Scene.update_geometry(hs) read.  Valid while this HostScene lives."""
+        n = self.desc.n_vertices
+        return np.ctypeslib.as_array(self.desc.positions, shape=(n, 3)) if n else np.zeros((0, 3))
+
+    def normals_view(self):
+        """The description's own normal array, as positions_view."""
+        n = self.desc.n_vertices
+        return np.ctypeslib.as_array(self.desc.normals, shape=(n, 3)) if n else np.zeros((0, 3))
+
     def indices(self):
         n = self.desc.n_triangles
         return np.ctypeslib.as_array(self.desc.indices, shape=(n, 3)).copy() if n else np.zeros((0, 3), np.int32)
@@ -182,6 +193,30 @@ class Scene:
         info = LjSceneInfo()
         _check(lib.lj_scene_info(self._h, C.byref(info)))
         self.info = info
+
+    def update_geometry(self, host_scene_or_desc):
+        """The scene with its vertices moved: `host_scene_or_desc` is the uploaded description with other positions, normals or sphere
+        positions / radii (HostScene.positions_view()); everything derived from them is re-derived and the BVHs are refitted on the device,
+        nothing else is rebuilt (lj_scene_update_geometry).  Later renders and queries see the new geometry, bit-identical to a fresh
+        Scene of the same description.  A refused update (LajollaError, LJ_ERR_INVALID_ARG) leaves the scene as it was."""
+        lib = load_library()
+        desc_ptr = host_scene_or_desc.desc_ptr if isinstance(host_scene_or_desc, HostScene) else C.pointer(host_scene_or_desc)
+        _check(lib.lj_scene_update_geometry(self._h, desc_ptr))
+        info = LjSceneInfo()
+        _check(lib.lj_scene_info(self._h, C.byref(info)))
+        self.info = info
+
+
+def read_bvh(scene, which):
+    """An acceleration structure as it stands on the device, as a uint8 array: which = 0 the BVH4 (128-byte DNode4 records), 1 the BVH8
+    (80-byte DNode8 records), 2 a tiny scene's leaf table (32-byte DScanLeaf records; empty for other scenes).  For tests."""
+    lib = load_library()
+    n = C.c_int64()
+    _check(lib.lj_scene_read_bvh(scene._h, int(which), None, 0, C.byref(n)))
+    out = np.zeros(n.value, np.uint8)
+    if n.value:
+        _check(lib.lj_scene_read_bvh(scene._h, int(which), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return out
 
 
 def make_args(spp=0, max_depth=None, rank=0, world_size=1, crop=None, pool_paths=0, seed=0, flags=0, rng_mode=_abi.LJ_RNG_SAMPLE):

@@ -224,6 +224,8 @@ SYMBOLS = [
     ("lj_camera_look_at", C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                     C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(LjCamera)]),
     ("lj_scene_set_camera", C.c_int, [C.c_void_p, C.POINTER(LjCamera)]),
+    ("lj_scene_update_geometry", C.c_int, [C.c_void_p, C.POINTER(LjSceneDesc)]),
+    ("lj_scene_read_bvh", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lj_render_views", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p]),
     ("lj_render_views_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p, C.c_void_p]),
     ("lj_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

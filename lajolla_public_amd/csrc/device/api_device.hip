@@ -3,6 +3,9 @@
 // torch.distributed over RCCL, see bench.py).  Every HIP call is checked; failures surface as LJ_ERR_DEVICE with
 // the HIP error string — there is no CPU fallback behind any of these functions.
 #include "api_internal.h"
+#include <chrono>
+#include <mutex>
+#include <set>
 
 namespace {
 
@@ -527,6 +530,12 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
     st.queue_bytes = st.extend_bytes + st.shade_bytes;
 }
 
+// The uploaded scenes of this process: lj_scene_update_geometry and lj_scene_read_bvh look a handle up before they touch it, so that a
+// destroyed one is an error and not a use after free.
+std::mutex g_live_mutex;
+std::set<const lj_scene *> g_live_scenes;
+bool scene_is_live(const lj_scene *sc) { std::lock_guard<std::mutex> lock(g_live_mutex); return sc && g_live_scenes.count(sc) != 0; }
+
 } // namespace
 
 extern "C" {
@@ -631,6 +640,7 @@ int lj_scene_upload(lj_context *ctx, const LjSceneDesc *desc, lj_scene **out) {
         }
         ctx->live_scenes++;
         *out = sc.release();
+        { std::lock_guard<std::mutex> lock(g_live_mutex); g_live_scenes.insert(*out); }
     });
 }
 
@@ -639,6 +649,7 @@ void lj_scene_destroy(lj_scene *scene) {
     lj_context *ctx = scene->ctx;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
+    { std::lock_guard<std::mutex> lock(g_live_mutex); g_live_scenes.erase(scene); }
     delete scene;
     if (--ctx->live_scenes == 0 && ctx->doomed) lj_context_destroy(ctx);
 }
@@ -688,6 +699,76 @@ int lj_scene_set_camera(lj_scene *scene, const LjCamera *camera) {
         const ljd::DScene h = F.host_view();
         scene->dscene.cam = h.cam; scene->dscene.init_spread = h.init_spread; scene->dscene.cam_medium = h.cam_medium;
         if (resized) { scene->plan_pixels.reset(); scene->plan_pixels_key = 0; scene->views_pixels.reset(); scene->views_pixels_key = 0; }   // lists of the old film
+    });
+}
+
+int lj_scene_update_geometry(lj_scene *scene, const LjSceneDesc *desc) {
+    return lj::guard([&]() {
+        if (!scene || !desc) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_update_geometry: null argument");
+        if (!scene_is_live(scene)) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_update_geometry: not an uploaded scene (destroyed?)");
+        const auto t0 = std::chrono::steady_clock::now();
+        lj::FlatScene &F = scene->flat;
+        // ---- host: every check, and everything lj_scene_upload derives from positions.  Nothing of the scene is touched before this returns.
+        lj::FlatScene U = lj::flatten_update(F, *desc);
+        auto same = [](size_t a, size_t b) { if (a != b) throw LjError(LJ_ERR_INTERNAL, "lj_scene_update_geometry: a re-derived table changed its size"); };
+        same(U.leaf_prims.size(), F.leaf_prims.size()); same(U.prims.size(), F.prims.size()); same(U.spheres.size(), F.spheres.size()); same(U.lights.size(), F.lights.size());
+        same(U.light_cdf.size(), F.light_cdf.size()); same(U.light_tris.size(), F.light_tris.size()); same(U.light_tri_cdf.size(), F.light_tri_cdf.size());
+        const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        lj_context *ctx = scene->ctx;
+        set_device(ctx);
+        hipStream_t s = ctx->stream;
+        const size_t bb = ljd::refit_box_bytes();
+        if (!scene->refit_box4.p) {
+            scene->refit_box4.alloc(std::max<size_t>(F.nodes.size(), 1) * bb); scene->refit_box8.alloc(std::max<size_t>(F.nodes8.size(), 1) * bb);
+            upload(scene->refit_levels4, F.levels4, s); upload(scene->refit_levels8, F.levels8, s);
+        }
+        // ---- device, in stream order: the tables, then the boxes of the three structures from the new leaf-ordered primitives
+        HIP_CHECK(hipEventRecord(ctx->ev_begin, s));
+        auto put = [&](DevBuf &b, const auto &v) { HIP_CHECK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, s)); };
+        put(scene->leaf_prims, U.leaf_prims); put(scene->prims, U.prims); put(scene->spheres, U.spheres); put(scene->light_tris, U.light_tris);
+        put(scene->light_tri_cdf, U.light_tri_cdf); put(scene->lights, U.lights); put(scene->light_cdf, U.light_cdf);
+        const ljd::DPrim *lp = (const ljd::DPrim *)scene->leaf_prims.p; const ljd::DSphere *sp = (const ljd::DSphere *)scene->spheres.p;
+        if (!F.scan_leaves.empty()) ljd::launch_refit_scan((ljd::DScanLeaf *)scene->scan_leaves.p, lp, sp, F.n_scan_used, s);
+        for (size_t l = F.level4_first.size() - 1; l-- > 0;)
+            ljd::launch_refit4((ljd::DNode4 *)scene->nodes.p, scene->refit_box4.p, lp, sp, (const int32_t *)scene->refit_levels4.p + F.level4_first[l], F.level4_first[l + 1] - F.level4_first[l], s);
+        const int stride8 = scene->dscene.node8_stride;
+        for (size_t l = F.level8_first.size() - 1; l-- > 0;)
+            ljd::launch_refit8(scene->nodes8.p, stride8, scene->refit_box8.p, lp, sp, (const int32_t *)scene->refit_levels8.p + F.level8_first[l], F.level8_first[l + 1] - F.level8_first[l], s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ctx->ev_end, s));
+        // the host copy of the nodes follows the device's (lj_scene_info and the tests read it)
+        HIP_CHECK(hipMemcpyAsync(F.nodes.data(), scene->nodes.p, F.nodes.size() * sizeof(ljd::DNode4), hipMemcpyDeviceToHost, s));
+        if (stride8 == (int)sizeof(ljd::DNode8)) HIP_CHECK(hipMemcpyAsync(F.nodes8.data(), scene->nodes8.p, F.nodes8.size() * sizeof(ljd::DNode8), hipMemcpyDeviceToHost, s));
+        else HIP_CHECK(hipMemcpy2DAsync(F.nodes8.data(), sizeof(ljd::DNode8), scene->nodes8.p, (size_t)stride8, sizeof(ljd::DNode8), F.nodes8.size(), hipMemcpyDeviceToHost, s));
+        if (!F.scan_leaves.empty()) HIP_CHECK(hipMemcpyAsync(F.scan_leaves.data(), scene->scan_leaves.p, F.scan_leaves.size() * sizeof(ljd::DScanLeaf), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+        lj::commit_update(F, std::move(U));
+        scene->dscene.eps = (float)F.shadow_epsilon;
+        // LjStats of an update: render_ms = device time (copies of the tables and the refit launches), generate_ms = host time of the re-derivation
+        scene->stats = LjStats{}; scene->stats.render_ms = ms; scene->stats.generate_ms = host_ms;
+    });
+}
+
+int lj_scene_read_bvh(const lj_scene *scene, int32_t which, void *out_host, int64_t capacity_bytes, int64_t *bytes) {
+    return lj::guard([&]() {
+        if (!scene || !bytes) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_read_bvh: null argument");
+        if (!scene_is_live(scene)) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_read_bvh: not an uploaded scene (destroyed?)");
+        if (which < 0 || which > 2) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_read_bvh: which must be 0 (DNode4), 1 (DNode8) or 2 (DScanLeaf)");
+        const lj::FlatScene &F = scene->flat;
+        const size_t n = which == 0 ? F.nodes.size() : which == 1 ? F.nodes8.size() : F.scan_leaves.size();
+        const size_t rec = which == 0 ? sizeof(ljd::DNode4) : which == 1 ? sizeof(ljd::DNode8) : sizeof(ljd::DScanLeaf);
+        *bytes = (int64_t)(n * rec);
+        if (!out_host) return;   // (a size query)
+        if (capacity_bytes < *bytes) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_read_bvh: buffer too small");
+        if (n == 0) return;
+        lj_context *ctx = scene->ctx;
+        set_device(ctx);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        const void *src = which == 0 ? scene->nodes.p : which == 1 ? scene->nodes8.p : scene->scan_leaves.p;
+        const size_t pitch = which == 1 ? (size_t)scene->dscene.node8_stride : rec;
+        if (pitch == rec) HIP_CHECK(hipMemcpy(out_host, src, n * rec, hipMemcpyDeviceToHost));
+        else HIP_CHECK(hipMemcpy2D(out_host, rec, src, pitch, rec, n, hipMemcpyDeviceToHost));
     });
 }
 

@@ -40,6 +40,11 @@ void launch_tile_init(bool vol, void *cursors, const uint32_t *tiles, uint32_t n
 int tile_grid(uint32_t n_tiles, uint32_t lanes);
 void launch_tile(bool vol, const DScene &sc, const DTileJob &job, void *cursors, uint32_t lanes, uint32_t budget, uint32_t *alive, const ExtendConfig &cfg, int *spill, hipStream_t s);
 void tile_cursor_stats(bool vol, const void *cursors_host, uint32_t n, unsigned long long out[5]);
+// refit.hip: the refit of lj_scene_update_geometry (drefit.h); `list`: node indices of one tree level, box4 / box8: one refit_box_bytes() record per node
+size_t refit_box_bytes();
+void launch_refit4(DNode4 *nodes, void *box4, const DPrim *leaf_prims, const DSphere *spheres, const int32_t *list, int n, hipStream_t s);
+void launch_refit8(void *nodes8, int stride, void *box8, const DPrim *leaf_prims, const DSphere *spheres, const int32_t *list, int n, hipStream_t s);
+void launch_refit_scan(DScanLeaf *leaves, const DPrim *leaf_prims, const DSphere *spheres, int n, hipStream_t s);
 }
 
 using lj::LjError;
@@ -93,6 +98,7 @@ struct lj_scene {
     lj::FlatScene flat;  // host copy (tables for lj_scene_info; arrays already uploaded)
     DevBuf nodes, nodes8, leaf_prims, prims, spheres, materials, lights, light_cdf, light_tris, light_tri_cdf, images3, images1, texels, env_tables;
     DevBuf media, volume_data, shape_media, scan_leaves;
+    DevBuf refit_box4, refit_box8, refit_levels4, refit_levels8;   // lj_scene_update_geometry: per-node boxes and the level tables (allocated by the first update)
     ljd::DScene dscene{};
     ljd::ExtendConfig ecfg{};
     ljd::ShadeConfig scfg{};

@@ -51,19 +51,22 @@ LJ_HD float scan_box(const float (&b)[6], const ScanRay &r, float tnear, float t
     return __builtin_fmaf(tx, -1.0000005f, te);
 }
 
-#if !defined(__HIP_DEVICE_COMPILE__)
-// Host: the table's record of the box [lo, hi] (the builder's padded float box).  c = the float nearest the midpoint, h = the smallest
+// The table's record of the box [lo, hi] (the builder's padded float box): flatten.cpp on the host, and the refit of an updated scene
+// (drefit.h) on the device — contraction off, so that the two agree bit for bit.  c = the float nearest the midpoint, h = the smallest
 // float >= max(hi - c, c - lo) + kScanGrow (|c| + that) + kScanDrift, taken in double: [c - h, c + h] contains [lo, hi] with room for the
 // rounding of m (above) and for the 1e-18 clamp: a direction component of zero is traced as 1e-18, which drifts 1e-18 t off the true ray;
 // kScanDrift covers segments up to 1e6 long where the builder's pad does not (a flat box at coordinate zero is padded by 1e-30 only).
 // (A difference of two floats is exact in double unless their exponents lie more than 29 apart; scan_sub_up then returns the next double
 // above, found from the rounding error.)
 constexpr double kScanGrow = 64.0 / 16777216.0, kScanDrift = 1e-12;
-inline double scan_sub_up(double a, double b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+LJ_HD double scan_sub_up(double a, double b) {
     const double s = a - b, a1 = s + b, b1 = a1 - s, err = (a - a1) + (b1 - b);   // (TwoSum of a and -b: a - b = s + err exactly)
     return err > 0.0 ? nextafter(s, (double)INFINITY) : s;
 }
-inline void scan_leaf_from_box(const float lo[3], const float hi[3], float c[3], float h[3]) {
+LJ_HD void scan_leaf_from_box(const float lo[3], const float hi[3], float c[3], float h[3]) {
     for (int k = 0; k < 3; k++) {
         const double l = lo[k], u = hi[k];
         c[k] = (float)(0.5 * (l + u));
@@ -74,6 +77,8 @@ inline void scan_leaf_from_box(const float lo[3], const float hi[3], float c[3],
         h[k] = hk;
     }
 }
+#if defined(__clang__)
+#pragma clang fp contract(fast)
 #endif
 
 } // namespace ljd

@@ -280,6 +280,8 @@ struct Collapse {
     }
 };
 
+} // namespace
+
 // grid step exponent for one axis: the smallest e with 255 * 2^e >= extent (so every plane of the node fits 8 bits)
 int grid_exponent(double extent) {
     int e = -126;
@@ -288,8 +290,6 @@ int grid_exponent(double extent) {
     if (e > 127) throw LjError(LJ_ERR_UNSUPPORTED, "scene extent beyond the float range of the BVH grid");
     return e;
 }
-
-} // namespace
 
 void build_bvh(const std::vector<BuildPrim> &prims, int max_leaf, int max_depth,
                std::vector<ljd::DNode4> &nodes, std::vector<ljd::DNode8> &nodes8, std::vector<int> &leaf_order, int &depth_out, int &depth8_out) {

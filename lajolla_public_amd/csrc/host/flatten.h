@@ -37,6 +37,16 @@ struct FlatScene {
     double bounds_radius = 0, bounds_center[3] = {0, 0, 0}, shadow_epsilon = 0;
     // double-precision tables kept for inspection by tests (scene.cpp:47-52)
     std::vector<double> light_pmf_d, light_cdf_d, light_power_d;
+    // ---- what lj_scene_update_geometry needs of the upload (flatten_update below)
+    std::vector<int32_t> leaf_order;           // leaf_prims[i] is global primitive leaf_order[i] (the builder's leaf order)
+    // level tables of the two trees: the wide nodes grouped by depth (found by walking the stored nodes from the root), root level first;
+    // level l is levels[level_first[l] .. level_first[l + 1])
+    std::vector<int32_t> levels4, level4_first, levels8, level8_first;
+    std::vector<LjShape> shapes_sig;           // the uploaded shapes and (kind, shape_id) of the lights: what an update may not change
+    std::vector<int32_t> lights_sig;
+    int64_t n_vertices_sig = 0, n_index_triangles_sig = 0;
+    uint64_t topology_hash = 0;                // of the index and uv arrays
+    std::vector<double> env_total;             // per light: the environment map's table total (its power follows bounds_radius), else 0
     // a DScene whose pointers refer to the vectors above (host memory)
     ljd::DScene host_view() const;
 };
@@ -49,6 +59,20 @@ ljd::DCamera flatten_camera(const LjCamera &c);
 
 // Throws LjError(LJ_ERR_UNSUPPORTED) for variant alternatives the device path does not implement.
 FlatScene flatten_scene(const LjSceneDesc &d);
+
+// lj_scene_update_geometry, host part.  `prev` is the flattened upload of a description of which `d` may differ in positions, normals and
+// each sphere's position / radius only.  Verifies that (counts; per shape kind, ranges, has_normals / has_uvs, material, light and medium
+// ids; per light kind and shape_id; the index and uv arrays by their hash; finite numbers; a scene extent inside the BVH8 grid's exponent
+// range) and throws LjError(LJ_ERR_INVALID_ARG) otherwise; then re-derives, with the code flatten_scene runs, everything that depends on
+// positions: prims, spheres, leaf_prims (in prev's leaf order), light_tris, light_tri_cdf, lights, light_cdf, the double tables, bounds and
+// shadow_epsilon.  Reads the shapes, positions, normals, uvs, indices and lights of `d`; ignores camera, options, materials, images, media.
+// The result holds those fields only; nothing of `prev` is changed.  commit_update moves them into the scene (the boxes of the trees are
+// the caller's to refit: device/drefit.h).
+FlatScene flatten_update(const FlatScene &prev, const LjSceneDesc &d);
+void commit_update(FlatScene &scene, FlatScene &&update);
+
+// bvh.cpp: grid step exponent of one BVH8 axis, the smallest e >= -126 with 255 * 2^e >= extent; throws beyond 127
+int grid_exponent(double extent);
 
 // bvh.cpp — binned-SAH tree with spatial splits (SBVH) over padded float boxes, collapsed to a BVH4; fills nodes (breadth-first)
 // and leaf order.
