@@ -188,7 +188,9 @@ typedef struct lj_scene lj_scene;      /* device-resident Scene: flattened BVH +
 
 int lj_context_create(int device_id, lj_context **out);
 /* Lifetime: scenes keep their context alive.  Destroying a context (or a device group, below) that still has scenes only marks it; the
- * last lj_scene_destroy (lj_group_scene_destroy) releases it — any destruction order is safe, every handle is destroyed exactly once. */
+ * last lj_scene_destroy (lj_group_scene_destroy) releases it — any destruction order is safe, every handle is destroyed exactly once.
+ * Not thread-safe: the count of a context's live scenes is a plain field, so lj_scene_upload, lj_scene_destroy and lj_context_destroy on
+ * handles of ONE context must be serialised by the caller (as must every other call on one context: it has one stream and one workspace). */
 void lj_context_destroy(lj_context *ctx);
 
 /* Replaces Scene::Scene (scene.cpp:3-53): builds the BVH (instead of rtcCommitScene), the bounds sphere,
@@ -373,7 +375,10 @@ typedef struct LjMediumQuery { int32_t medium_id; float p[3], org[3], dir[3], tf
 typedef struct LjMediumResult { float sigma_s[3], sigma_a[3], majorant[3]; } LjMediumResult;
 int lj_medium_queries(lj_scene *scene, int64_t n, const LjMediumQuery *queries_host, LjMediumResult *results_host);
 
-/* Counters of the last lj_render* call. */
+/* Counters of the last lj_render* call — or of the last lj_intersect, lj_occluded or lj_scene_update_geometry, which overwrite them too:
+ * a ray query leaves render_ms = the query kernel's device time, rays_closest or rays_shadow = n, and mega_launches = 1 or
+ * extend_launches = 1 for the route that answered (a tiny scene's leaf scan, or the BVH traversal); an update leaves render_ms and
+ * generate_ms (see lj_scene_update_geometry).  Every other field is then 0.  Read the counters of a render before the next such call. */
 typedef struct LjStats {
     uint64_t samples;          /* camera samples traced (LJ_RNG_TILE: those of every tile walked, outside a crop window too) */
     uint64_t bounce_iterations;/* sum over samples of executed iterations of the loop at path_tracing.h:66 (K) */

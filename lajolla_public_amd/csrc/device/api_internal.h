@@ -1,6 +1,8 @@
-// Internals shared by the C-ABI translation units that own the GPU (api_device.hip: context, upload, render; queries.hip:
-// the batched per-object queries): HIP error boundary, device buffers, the context and scene objects behind the opaque
-// handles of include/lajolla_hip.h, and the kernel launchers of kernels.hip.
+// Internals shared by the C-ABI translation units that own the GPU (api_device.hip: context and scene lifetime, upload, geometry
+// update, ray queries and the extern "C" render entry points; render.hip: render plans and the five render drivers behind run_render;
+// queries.hip: the batched per-object queries): HIP error boundary, device buffers, the small helpers those files share, the context
+// and scene objects behind the opaque handles of include/lajolla_hip.h, the kernel launchers of kernels.hip and what render.hip
+// offers the entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../host/api_common.h"
@@ -60,6 +62,19 @@ struct DevBuf {
     DevBuf() = default; DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
 };
 
+// grow-only workspace: a buffer that already holds `bytes` is left alone
+inline void ensure(DevBuf &b, size_t bytes) { if (b.bytes < bytes) b.alloc(bytes); }
+
+// A developer switch: the integer the environment gives `name`, or `dflt` when it is unset.  Read at every call — tests and tools flip
+// LJ_TUNE_* between two renders of one process — and clamped where it is used.
+inline bool env_set(const char *name) { return getenv(name) != nullptr; }
+inline int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+// LJ_TUNE_MEGA=0: no scene takes the leaf-scan route of mega.hip — a render runs the wavefront kernels, a ray query k_extend's traversal
+inline bool mega_enabled() { return env_int("LJ_TUNE_MEGA", 1) != 0; }
+
 template <typename T> inline void upload(DevBuf &b, const std::vector<T> &v, hipStream_t s) {
     b.alloc(((std::max<size_t>(v.size(), 1) * sizeof(T)) + 31) & ~(size_t)15);
     if (!v.empty()) HIP_CHECK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
@@ -109,3 +124,30 @@ struct lj_scene {
     LjStats stats{};
 };
 
+inline void set_device(lj_context *ctx) { HIP_CHECK(hipSetDevice(ctx->device)); }
+
+inline float elapsed_ms(hipEvent_t from, hipEvent_t to) { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, from, to)); return ms; }
+// closes the timed region that a record of ev_begin opened on `s`: device milliseconds, after a wait for the region's end
+inline float close_timer(lj_context *ctx, hipStream_t s) {
+    HIP_CHECK(hipEventRecord(ctx->ev_end, s));
+    HIP_CHECK(hipEventSynchronize(ctx->ev_end));
+    return elapsed_ms(ctx->ev_begin, ctx->ev_end);
+}
+
+// ---- render.hip
+struct RenderPlan {
+    int spp; uint32_t pool; uint64_t seed;
+    std::shared_ptr<const std::vector<uint32_t>> pixels;  // rendered pixels in tile order (cached per scene: same share -> same list)
+    uint64_t pixels_key = 0;                               // identifies the list on the device (lj_context::pixel_list_key)
+    int max_depth;
+    int rng_mode;                                          // LJ_RNG_SAMPLE / LJ_RNG_TILE
+    int rank, world, cx0, cy0, cx1, cy1;                   // the share and the crop window (the full frame when there is none)
+    // a batch of cameras (lj_render_views): `pixels` lists e = v*w*h + y*w + x — the single-view list, in its order, once per view — and
+    // views_dev is the batch's camera table on the device (0 / null: the scene's one camera)
+    int n_views = 0; const ljd::DCamera *views_dev = nullptr;
+};
+inline bool timing_requested(const LjRenderArgs *a) { return a && (a->flags & 1u); }   // (LjRenderArgs::flags bit 0: time every kernel)
+RenderPlan make_plan(lj_scene *sc, const LjRenderArgs *a);
+RenderPlan make_views_plan(lj_scene *sc, const LjRenderArgs *a, int n_views);
+void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *samples_host, hipStream_t stream, bool timing);
+int *ensure_spill(lj_context *ctx, int levels, uint32_t grid);

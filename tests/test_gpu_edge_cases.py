@@ -162,3 +162,48 @@ def test_render_cut_into_passes(cbox):
     parts = lj.render(sc, spp=spp, rank=0, world_size=2) + lj.render(sc, spp=spp, rank=1, world_size=2)
     same = bool(np.array_equal(whole, parts))
     assert same and bool(np.isfinite(whole).all())
+
+
+PASS_CROP = (248, 252, 264, 260)   # 16 x 8 pixels in the middle of the 512 x 512 film
+
+
+@pytest.mark.parametrize("route", ["mega", "wavefront", "volpath"])
+def test_pass_boundaries_do_not_change_a_sample(cbox, monkeypatch, route):
+    """Per-sample radiance of a 16 x 8 crop at 5 spp, in one pass and cut into 11 passes of 12 pixels (the last of 8): every pass's samples
+    land at its own place in the host array.  Through k_mega, through the wavefront driver at its smallest geometry (one workgroup, one
+    lane) and through the volumetric kernel."""
+    from views_common import scene_file
+    sc = lj.Scene(lj.Context(0), lj.parse_scene(scene_file("vol_cbox"))) if route == "volpath" else cbox[1]
+    if route == "wavefront":
+        monkeypatch.setenv("LJ_TUNE_MEGA", "0")
+    monkeypatch.delenv("LJ_TUNE_PASS_SAMPLES", raising=False)
+    whole = lj.render_samples(sc, PASS_CROP, spp=5)
+    assert sc.stats().samples == 16 * 8 * 5
+    monkeypatch.setenv("LJ_TUNE_PASS_SAMPLES", "64")
+    cut = lj.render_samples(sc, PASS_CROP, spp=5)
+    st = sc.stats()
+    print(route, st.samples, st.wavefront_steps, float(whole.mean()))
+    assert st.samples == 16 * 8 * 5 and st.wavefront_steps >= 11
+    same = bool(np.array_equal(whole.view(np.uint32), cut.view(np.uint32)))
+    assert same and bool(np.isfinite(whole).all())
+
+
+@pytest.mark.parametrize("mega", [True, False])
+def test_instrumented_render_is_the_same_render(cbox, monkeypatch, mega):
+    """flags=1 (HIP events around every launch, the per-kernel figures of bench.py) renders the very image of flags=0 and fills the
+    per-kernel fields of LjStats; flags=0 leaves the per-kernel times zero."""
+    hs, sc, o = cbox
+    if not mega:
+        monkeypatch.setenv("LJ_TUNE_MEGA", "0")
+    plain = lj.render(sc, spp=4, crop=(0, 0, 64, 64), flags=0)
+    s0 = sc.stats()
+    timed = lj.render(sc, spp=4, crop=(0, 0, 64, 64), flags=1)
+    s1 = sc.stats()
+    print(mega, s1.mega_ms, s1.mega_launches, s1.extend_ms, s1.shade_ms, s1.extend_launches, s1.shade_launches)
+    same = bool(np.array_equal(plain.view(np.uint32), timed.view(np.uint32)))
+    assert same
+    if mega:
+        assert s1.mega_ms > 0 and s1.mega_launches == 1
+    else:
+        assert s1.extend_ms > 0 and s1.shade_ms > 0 and s1.extend_launches == s1.shade_launches > 0
+        assert s0.extend_ms == 0 and s0.shade_ms == 0
