@@ -1,8 +1,8 @@
 // Internals shared by the C-ABI translation units that own the GPU (api_device.hip: context and scene lifetime, upload, geometry
 // update, ray queries and the extern "C" render entry points; render.hip: render plans and the five render drivers behind run_render;
 // queries.hip: the batched per-object queries): HIP error boundary, device buffers, the small helpers those files share, the context
-// and scene objects behind the opaque handles of include/lajolla_hip.h, the kernel launchers of kernels.hip and what render.hip
-// offers the entry points.
+// and scene objects behind the opaque handles of include/lajolla_hip.h, the kernel launchers of kernels.hip (shade, tail, resolve),
+// extend.hip (extend, aux, ray queries and their launch plan) and the other kernel files, and what render.hip offers the entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../host/api_common.h"
@@ -17,6 +17,7 @@
 #include <vector>
 
 namespace ljd {
+// kernels.hip (shade_*, launch_shade / _tail / _resolve) and extend.hip (extend_config, max_stack_depth, launch_extend / _aux / _trace_rays)
 ShadeConfig shade_config(size_t n_prims, size_t n_materials, size_t n_lights, size_t n_light_tris, size_t n_light_tri_cdf, size_t n_images3, size_t n_images1, size_t n_env_marg);
 int shade_variant(uint32_t kinds, bool textured, bool envmap, bool sphere_lights);
 ExtendConfig extend_config(int n_nodes, int n_prims, int bvh_depth, int n_spheres, int n_nodes8, int bvh8_depth, bool open_scene);

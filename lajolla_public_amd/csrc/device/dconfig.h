@@ -1,4 +1,4 @@
-// Launch plans decided at scene upload (kernels.hip, mega.hip) and carried by the scene object (api_internal.h).
+// Launch plans decided at scene upload (extend.hip, kernels.hip, mega.hip) and carried by the scene object (api_internal.h).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

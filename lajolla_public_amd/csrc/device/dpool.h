@@ -1,4 +1,4 @@
-// Pieces shared by the extend kernels of kernels.hip (BVH4, trees inside the LDS image) and extend8.hip (BVH8, trees beyond it): queue
+// Pieces shared by the extend kernels of extend.hip (BVH4, trees inside the LDS image) and extend8.hip (BVH8, trees beyond it): queue
 // record helper, the batched-query records, and the pooled leaf phase — a wave lists its (ray, primitive) pairs in LDS and tests them 64 at
 // a time on whichever lane is free.
 #pragma once
@@ -22,9 +22,6 @@ struct HitIO { float t, u, v; int32_t shape_id, prim_id; };
 // its (ray, primitive) pairs in LDS and tests them 64 at a time on whichever lane is free; the ray of a pair comes from its owner's
 // registers (ds_bpermute), results are merged per owner by one 64-bit LDS minimum on (t, global primitive id) — the same order the
 // lane-by-lane test applies, so the hit record is the same, bit for bit — and the winner leaves its unnormalised barycentrics beside it.
-#ifndef LJ_EXT_POOL
-#define LJ_EXT_POOL 1
-#endif
 constexpr uint32_t kPoolCap = 256;                                      // pairs listed at a time (a wave holds at most 64 x 16: a held leaf and the one a lane sits on)
 constexpr uint32_t kWavePoolBytes = 64 * 8 + 64 * 16 + kPoolCap * 4;    // keys | winners (U, V, S, t) | items (owner lane | leaf-order primitive index << 6)
 struct LeafPool { LJ_LDS unsigned long long *keys; LJ_LDS v4f *win; LJ_LDS uint32_t *items; };

@@ -1,4 +1,4 @@
-// Device helpers shared by the kernel translation units (kernels.hip: the wavefront kernels; mega.hip: the fused kernel of tiny
+// Device helpers shared by the kernel translation units (kernels.hip, extend.hip: the wavefront kernels; mega.hip: the fused kernel of tiny
 // scenes): LDS address-space shorthands, bit casts, a wave-wide sum and the per-workgroup LDS staging of the shading tables.
 #pragma once
 #include <hip/hip_runtime.h>

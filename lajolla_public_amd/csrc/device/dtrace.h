@@ -113,7 +113,7 @@ LJ_HD bool leaf_prim_test(Mem &mem, const RayF &ray, const DPrim &p, HitRec &bes
     return false;
 }
 
-// Reference form of the traversal the extend kernel performs (kernels.hip keeps a wave-synchronous version of the same
+// Reference form of the traversal the extend kernel performs (extend.hip keeps a wave-synchronous version of the same
 // steps): hit children are visited nearest first, the others wait on the stack.
 // Mem provides: DNode4 node(int i); DPrim prim(int i); const DSphere& sphere(int slot);
 //               void push(int sp, int v); int pop(int sp);   (per-lane stack storage, 3 * bvh depth entries)
@@ -205,7 +205,7 @@ LJ_HD Ray8 ray8_setup(const RayF &ray) {
 LJ_HD int ctz32(uint32_t v) { return __builtin_ctz(v); }
 LJ_HD int popc32(uint32_t v) { return __builtin_popcount(v); }
 
-// Reference form of the BVH8 traversal (kernels.hip keeps a wave-synchronous version of the same steps).  A node group is
+// Reference form of the BVH8 traversal (extend8.hip keeps a wave-synchronous version of the same steps).  A node group is
 // (child_base, remaining inner hits in octant order | imask << 8): one stack entry per visited node, however many of its children were hit.
 // Mem provides: const uint32_t *node8(int i); DPrim prim(int i); const DSphere& sphere(int slot);
 //               void push8(int sp, uint32_t base, uint32_t bits); void pop8(int sp, uint32_t &base, uint32_t &bits);

@@ -37,10 +37,7 @@ struct DevTracer {
         L.ray.ox = org.x; L.ray.oy = org.y; L.ray.oz = org.z; L.ray.dx = dir.x; L.ray.dy = dir.y; L.ray.dz = dir.z;
         trav_begin(L, tnear, tfar);
         tick(2);
-        while (L.cur != kDone) {
-            while (L.cur >= 0 && L.cur != kDone) { tick(0); trav_node_step<false>(tv, L); }
-            if (L.cur < 0) { tick(1); trav_leaf_step<false, SPHERES == 1>(tv, L, false); }
-        }
+        trace_lane<SPHERES == 1>(tv, L, false, [&](int s) { tick(s); });
         trav_finish(L);
         t = L.best.t; u = L.best.u; v = L.best.v; gprim = L.best.gprim;
         if (SPHERES == 2) {

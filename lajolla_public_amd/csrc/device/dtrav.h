@@ -1,6 +1,7 @@
-// BVH4 traversal steps shared by the kernels that walk the flattened tree (kernels.hip: k_extend, k_tail, k_trace_rays, k_aux;
-// volpath.hip: the volumetric path tracer): the LDS image of a workgroup (per-lane stacks, the top of the tree, small scenes' primitives),
-// one inner-node step, one leaf step, the pooled leaf phase.  Device code only.
+// BVH4 traversal steps shared by the kernels that walk the flattened tree (extend.hip: k_extend, k_trace_rays, k_aux; kernels.hip: k_tail;
+// volpath.hip / tile.hip: the per-lane tracer of dtracer.h): the LDS image of a workgroup (per-lane stacks, the top of the tree, small
+// scenes' primitives), one inner-node step, one leaf step, the lane-by-lane loop over them (trace_lane), the pooled leaf phase, and the
+// BVH4 as a Walk of the wave-synchronous driver (Walk4, dextend.h).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dpool.h"
@@ -95,13 +96,7 @@ __device__ __forceinline__ int trav_pop(const TreeView &tv, LaneTrav &L) {
 // A ray that reaches a leaf sets it aside and goes on with the next entry of its stack; it only has to wait for the wave's leaf phase when
 // it reaches a second one.  The lanes of a wave then spend more node steps together before the leaf phase (which finds fuller rounds), at
 // the price of the node steps a hit in the held leaf would have culled.  The closest hit is the minimum of (t, primitive id) over
-// everything the ray tests, so the order of the tests cannot change it.
-#ifndef LJ_EXT_HOLD
-#define LJ_EXT_HOLD 1
-#endif
-#ifndef LJ_EXT_HOLD_SHADOW
-#define LJ_EXT_HOLD_SHADOW 1   // any-hit rays hold a leaf too (0: they wait at their first leaf — a hit there ends them)
-#endif
+// everything the ray tests, so the order of the tests cannot change it.  Any-hit rays hold a leaf too (a hit in it would have ended them).
 template <bool RESIDENT>
 __device__ __forceinline__ void trav_hold(const TreeView &tv, LaneTrav &L) {
     L.held = L.cur;
@@ -114,19 +109,9 @@ __device__ __forceinline__ void trav_finish(LaneTrav &L) {
     L.best.u = L.best.u * rS; L.best.v = L.best.v * rS;
 }
 
-#ifndef LJ_EXT_CSW_MINMAX
-#define LJ_EXT_CSW_MINMAX 0   // 1: the distances of a compare-exchange are taken as min / max (nothing waits on the comparison's mask)
-#endif
-#ifndef LJ_EXT_SORT
-#define LJ_EXT_SORT 5         // compare-exchanges of a node step: 5 = the four children fully ordered; 4 = nearest and farthest in place; 3 = nearest only
-#endif
 __device__ __forceinline__ void csw(float &ta, int &ca, float &tb, int &cb) {  // compare-exchange: nearer entry first
     const bool sw = tb < ta;
-#if LJ_EXT_CSW_MINMAX
-    const float t0 = fminf(ta, tb), t1 = fmaxf(ta, tb);   // (entry distances are numbers: same values as the selects)
-#else
     const float t0 = sw ? tb : ta, t1 = sw ? ta : tb;
-#endif
     const int c0 = sw ? cb : ca, c1 = sw ? ca : cb;
     ta = t0; tb = t1; ca = c0; cb = c1;
 }
@@ -135,16 +120,13 @@ __device__ __forceinline__ void csw(float &ta, int &ca, float &tb, int &cb) {  /
 // The stack part of the step is free of branches whenever the three pushes of every lane stay inside the LDS levels (always, when
 // the scene is RESIDENT — the whole tree and every stack level in LDS; else a wave-uniform test, which only a ray deeper than
 // `cap - 3` entries fails): the pushes store unconditionally and advance `sp` only for a hit, and the pop candidate is fetched with the node.
-#ifndef LJ_EXT_LDS_NODES
-#define LJ_EXT_LDS_NODES 1   // 0: a tree that is not fully LDS-resident is read through L1 / L2 only (no LDS copy of its top)
-#endif
 template <bool RESIDENT>
 __device__ __forceinline__ void trav_node_step(const TreeView &tv, LaneTrav &L) {
     v4f nx, ny, nz, fx, fy, fz, ch;
     const int i = L.cur;
     int popped = kDone;
     const bool fast = RESIDENT || __ballot(L.sp + 3 > tv.cap) == 0ull;
-    if (RESIDENT || (LJ_EXT_LDS_NODES && i < tv.n_lnodes)) {
+    if (RESIDENT || i < tv.n_lnodes) {
         const LJ_LDS char *b = tv.lnodes + (uint32_t)i * 16u;
         const uint32_t S = tv.qstride;
         nx = *(const LJ_LDS v4f *)(b + L.nqx * S); fx = *(const LJ_LDS v4f *)(b + (3u - L.nqx) * S);
@@ -172,13 +154,8 @@ __device__ __forceinline__ void trav_node_step(const TreeView &tv, LaneTrav &L) 
     }
     // (an entry distance is finite for a hit: it is bounded by best.t or by the finite far planes)
     csw(t0[0], c[0], t0[1], c[1]); csw(t0[2], c[2], t0[3], c[3]);
-    csw(t0[0], c[0], t0[2], c[2]);
-#if LJ_EXT_SORT >= 4
-    csw(t0[1], c[1], t0[3], c[3]);
-#endif
-#if LJ_EXT_SORT >= 5
-    csw(t0[1], c[1], t0[2], c[2]);
-#endif
+    csw(t0[0], c[0], t0[2], c[2]); csw(t0[1], c[1], t0[3], c[3]);
+    csw(t0[1], c[1], t0[2], c[2]);   // the four children fully ordered
     if (fast) {
         const int sp0 = L.sp;
         tv.stack[L.sp * kBlock] = c[3]; L.sp += (t0[3] < inf) ? 1 : 0;   // misses sort last: a slot written for a miss is
@@ -235,6 +212,18 @@ __device__ __forceinline__ void trav_leaf_step(const TreeView &tv, LaneTrav &L, 
     L.cur = stop ? kDone : trav_pop<RESIDENT>(tv, L);
 }
 
+// One lane's ray from trav_begin to the end of its traversal, lane by lane: what the kernels that keep a whole path in one lane run
+// (k_tail, k_aux, the tracer of dtracer.h).  A closest-hit query calls trav_finish afterwards.
+// `tick(0)` / `tick(1)` before every node / leaf step: the tracer's developer counters (nothing by default).
+struct NoTick { __device__ __forceinline__ void operator()(int) const {} };
+template <bool SPHERES = true, class Tick = NoTick>
+__device__ __forceinline__ void trace_lane(const TreeView &tv, LaneTrav &L, const bool any_hit, Tick tick = Tick()) {
+    while (L.cur != kDone) {
+        while (L.cur >= 0 && L.cur != kDone) { tick(0); trav_node_step<false>(tv, L); }
+        if (L.cur < 0) { tick(1); trav_leaf_step<false, SPHERES>(tv, L, any_hit); }
+    }
+}
+
 // Called by the whole wave.  `at_leaf`: this lane's L.cur is a leaf.  Returns the number of
 // 64-pair rounds it ran (for the statistics); `n_pairs` the pairs.
 template <bool RESIDENT, bool SPHERES>
@@ -274,5 +263,24 @@ __device__ __forceinline__ uint32_t trav_leaf_pool(const TreeView &tv, const Lea
     }
     return rounds;
 }
+
+// The BVH4 as a Walk of the wave-synchronous driver (extend_loop, dextend.h).  at_leaf: the lane sits on a leaf or holds one.
+template <bool RESIDENT, bool SPHERES>
+struct Walk4 {
+    using View = TreeView;
+    using Lane = LaneTrav;
+    static __device__ __forceinline__ void idle(LaneTrav &L) { L.cur = kDone; L.sp = 0; L.held = 0; }
+    static __device__ __forceinline__ void begin(LaneTrav &L, float tnear, float tfar) { trav_begin(L, tnear, tfar); }
+    static __device__ __forceinline__ void hold(const TreeView &tv, LaneTrav &L, const bool busy) { if (busy && L.cur < 0 && L.held == 0) trav_hold<RESIDENT>(tv, L); }
+    static __device__ __forceinline__ bool descending(const LaneTrav &L) { return L.cur >= 0 && L.cur != kDone; }
+    static __device__ __forceinline__ void node_step(const TreeView &tv, LaneTrav &L) { trav_node_step<RESIDENT>(tv, L); }
+    static __device__ __forceinline__ bool at_leaf(const LaneTrav &L) { return L.cur < 0 || L.held != 0; }
+    static __device__ __forceinline__ uint32_t leaf_pool(const TreeView &tv, const LeafPool &lp, LaneTrav &L, const bool at_leaf, const bool any_hit, uint32_t &n_pairs) {
+        return trav_leaf_pool<RESIDENT, SPHERES>(tv, lp, L, at_leaf, any_hit, n_pairs);
+    }
+    static __device__ __forceinline__ bool finished(const LaneTrav &L) { return L.cur == kDone; }
+    static __device__ __forceinline__ void rearm(LaneTrav &L) { L.cur = 0; }
+    static __device__ __forceinline__ void finish(LaneTrav &L) { trav_finish(L); }
+};
 
 } // namespace ljd

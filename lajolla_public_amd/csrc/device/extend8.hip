@@ -3,11 +3,12 @@
 // (intersection.cpp:7-85; what rtcIntersect1 / rtcOccluded1 do for the reference)
 #include <hip/hip_runtime.h>
 #include "dpool.h"
+#include "dextend.h"
 
 namespace ljd {
 
 // ---------------------------------------------------------------- extend over the BVH8 (trees beyond the LDS image)
-// The same wave-synchronous scheme as k_extend — persistent waves, dynamic refill, a node phase and a pooled leaf phase — over DNode8
+// The wave-synchronous scheme of k_extend (extend_loop, dextend.h) — persistent waves, dynamic refill, a node phase and a pooled leaf phase — over DNode8
 // (dtypes.h): a step gathers 80 bytes (five dwordx4) instead of 112 and tests eight quantised children, a ray takes ~0.7x as many steps
 // (sponza: 12.3 instead of 17.0 per extension ray), and the stack holds node GROUPS (child_base, remaining hit children in octant order |
 // imask << 8) — at most one push per step, one 8-byte entry.  Leaf children that are hit are not tested at once: the lane notes
@@ -164,107 +165,34 @@ __device__ __forceinline__ uint32_t trav8_leaf_pool(const Tree8View &tv, const L
     return rounds;
 }
 
+// The BVH8 as a Walk of the wave-synchronous driver (extend_loop, dextend.h).  A lane descends while it has an open group and room for another pending
+// leaf group; at_leaf: it has pending leaf groups; nothing is held aside before the node phase (leaf hits are noted by the node step).
+template <bool SPHERES>
+struct Walk8 {
+    using View = Tree8View;
+    using Lane = LaneTrav8;
+    static __device__ __forceinline__ void idle(LaneTrav8 &L) { L.gbits = 0u; L.gbase = 0u; L.pendA = 0u; L.pendB = 0u; L.sp = 0; }
+    static __device__ __forceinline__ void begin(LaneTrav8 &L, float tnear, float tfar) { trav8_begin(L, tnear, tfar); }
+    static __device__ __forceinline__ void hold(const Tree8View &, LaneTrav8 &, const bool) {}
+    static __device__ __forceinline__ bool descending(const LaneTrav8 &L) { return trav8_descending(L); }
+    static __device__ __forceinline__ void node_step(const Tree8View &tv, LaneTrav8 &L) { trav8_node_step(tv, L); }
+    static __device__ __forceinline__ bool at_leaf(const LaneTrav8 &L) { return L.pendA != 0u; }
+    static __device__ __forceinline__ uint32_t leaf_pool(const Tree8View &tv, const LeafPool &lp, LaneTrav8 &L, const bool at_leaf, const bool any_hit, uint32_t &n_pairs) {
+        return trav8_leaf_pool<SPHERES>(tv, lp, L, at_leaf, any_hit, n_pairs);
+    }
+    static __device__ __forceinline__ bool finished(const LaneTrav8 &L) { return trav8_finished(L); }
+    static __device__ __forceinline__ void rearm(LaneTrav8 &L) { L.gbits = 1u; }
+    static __device__ __forceinline__ void finish(LaneTrav8 &L) { trav8_finish(L); }
+};
+
 #ifndef LJ_EXT8_OCC
 #define LJ_EXT8_OCC 5   // 91 - 95 VGPRs: five waves per SIMD, as many as five 30-KiB workgroups per CU bring
 #endif
 template <bool STATS, bool SPHERES>
 __global__ void __launch_bounds__(kBlock, STATS ? 4 : LJ_EXT8_OCC) k_extend8(DScene sc, DQueue q, const DBlockState *blocks, uint32_t seg, uint32_t *work, const uint32_t *chunk_list, uint32_t parity, int stack, int lds_nodes, unsigned long long *spill, uint32_t refill_min, uint32_t min_descending, unsigned long long *stats, uint32_t pool_at) {
-    unsigned long long st_outer = 0, st_busy = 0, st_nodes = 0, st_node_lanes = 0, st_leaf = 0, st_leaf_lanes = 0, st_refill = 0, st_rays = 0;
     const Tree8View tv = stage_tree8(sc, stack, lds_nodes, spill, gridDim.x * kBlock, blockIdx.x * kBlock + threadIdx.x);
     const LeafPool lp = leaf_pool_at(pool_at);
-    // (work distribution, refill and ray set-up: exactly k_extend's — see the comments there)
-    const uint32_t n_chunks = work[1 + parity];
-    if (blockIdx.x == 0 && threadIdx.x == 0) work[1 + (parity ^ 1u)] = 0u;
-    uint32_t *chunk_counter = work;
-    const bool leader = (threadIdx.x & 63u) == 0u;
-    const uint32_t n_waves = gridDim.x * (kBlock / 64u);
-    const bool draw = n_chunks > n_waves;
-    uint32_t pre = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6);
-    uint32_t next = 0, end = 0;
-    bool exhausted = false;
-    bool busy = false; int phase = 0; uint32_t path = 0; uint32_t flags = 0; int vis = 0; int start = 0;
-    float edx = 0, edy = 0, edz = 0;
-    LaneTrav8 L; L.gbits = 0u; L.gbase = 0u; L.pendA = 0u; L.pendB = 0u; L.sp = 0;
-    for (;;) {
-        if (next == end && !exhausted) {
-            const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)pre);
-            if (c >= n_chunks) exhausted = true;
-            else {
-                const uint32_t slot0 = chunk_list[c] * kChunk, b = slot0 / seg, off = slot0 - b * seg, cnt = blocks[b].count;
-                const uint32_t live = cnt > off ? (cnt - off < kChunk ? cnt - off : kChunk) : 0u;
-                next = slot0; end = slot0 + live;
-                if (draw) { if (leader) pre = atomicAdd(chunk_counter, 1u); }
-                else pre = 0xffffffffu;
-                if (live == 0u) continue;
-            }
-        }
-        const unsigned long long idle = __ballot(!busy);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        const uint32_t left = end - next;
-        if (left > 0 && (n_idle >= refill_min || n_idle == 64u)) {
-            if (STATS) st_refill++;
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-            const bool take = !busy && rank < left;
-            if (take) {
-                path = next + rank;
-                const Rec4 ro = q.ro[path], rd = q.rd[path];
-                L.ray.ox = ro.x; L.ray.oy = ro.y; L.ray.oz = ro.z;
-                edx = rd.x; edy = rd.y; edz = rd.z; flags = f2u(rd.w);
-                vis = 0; busy = true;
-                if (ro.w > 0.0f) {
-                    const Rec4 rs = q.rs[path];
-                    L.ray.dx = rs.x; L.ray.dy = rs.y; L.ray.dz = rs.z; L.ray.tfar = ro.w;
-                    start = 1;
-                } else if (!(flags & PF_NO_EXT)) start = 2;
-                else { q.rh[path] = mk4(0.0f, 0.0f, 0.0f, u2f(0u)); busy = false; }
-            }
-            next += n_idle < left ? n_idle : left;
-        }
-        if (start != 0) {
-            const bool ext = start == 2;
-            if (ext) { L.ray.dx = edx; L.ray.dy = edy; L.ray.dz = edz; }
-            trav8_begin(L, (ext && (flags & 0xffffu) == 2u) ? 0.0f : sc.eps, ext ? INFINITY : L.ray.tfar);
-            phase = ext ? 1 : 0; start = 0;
-        }
-        if (__ballot(busy) == 0ull) { if (exhausted && next == end) break; else continue; }
-        if (STATS) { st_outer++; st_busy += __popcll(__ballot(busy)); }
-        // ---- node phase: lanes with an open group and room for another pending leaf group step; once few of them are left and somebody
-        // has leaves to test, the wave moves on
-        for (;;) {
-            const bool descending = busy && trav8_descending(L);
-            const unsigned long long dm = __ballot(descending);
-            if (dm == 0ull) break;
-            if ((uint32_t)__popcll(dm) < min_descending && __ballot(busy && L.pendA != 0u) != 0ull) break;
-            if (STATS) { st_nodes++; st_node_lanes += __popcll(dm); }
-            if (descending) trav8_node_step(tv, L);
-        }
-        // ---- pooled leaf phase
-        {
-            uint32_t n_pairs;
-            const uint32_t rounds = trav8_leaf_pool<SPHERES>(tv, lp, L, busy && L.pendA != 0u, phase == 0, n_pairs);
-            if (STATS) { st_leaf += rounds; st_leaf_lanes += n_pairs; }
-        }
-        // ---- ray finished?
-        const bool fin = busy && trav8_finished(L);
-        if (STATS) st_rays += __popcll(__ballot(fin));
-        if (fin) {
-            if (phase == 0) {
-                vis = (L.best.gprim < 0) ? HIT_VIS_BIT : 0;
-                if (!(flags & PF_NO_EXT)) { start = 2; L.gbits = 1u; }   // (not "finished" any more: this block must not run twice)
-                else { q.rh[path] = mk4(0.0f, 0.0f, 0.0f, u2f((uint32_t)vis)); busy = false; }
-            } else {
-                const uint32_t code = (uint32_t)vis | (uint32_t)(L.best.gprim + 1);
-                const bool hit = L.best.gprim >= 0;
-                trav8_finish(L);
-                q.rh[path] = mk4(hit ? L.best.t : 0.0f, L.best.u, L.best.v, u2f(code));
-                busy = false;
-            }
-        }
-    }
-    if (STATS && (threadIdx.x & 63) == 0) {
-        atomicAdd(&stats[0], st_outer); atomicAdd(&stats[1], st_busy); atomicAdd(&stats[2], st_nodes); atomicAdd(&stats[3], st_node_lanes);
-        atomicAdd(&stats[4], st_leaf); atomicAdd(&stats[5], st_leaf_lanes); atomicAdd(&stats[6], st_refill); atomicAdd(&stats[7], st_rays);
-    }
+    extend_loop<STATS, Walk8<SPHERES>>(tv, lp, sc, q, blocks, seg, work, chunk_list, parity, refill_min, min_descending, stats);
 }
 
 // (the same queries over the BVH8, with k_extend8's two phases: what lj_intersect / lj_occluded run for a tree beyond the LDS image)
@@ -275,13 +203,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays8(DScene sc, const RayIO *
         const long long i = i0 + threadIdx.x;
         const bool act = i < n;
         LaneTrav8 L;
-        L.ray.ox = 0.0f; L.ray.oy = 0.0f; L.ray.oz = 0.0f; L.ray.dx = 0.0f; L.ray.dy = 0.0f; L.ray.dz = 1.0f;
-        if (act) {
-            L.ray.ox = rays[i].org[0]; L.ray.oy = rays[i].org[1]; L.ray.oz = rays[i].org[2];
-            L.ray.dx = rays[i].dir[0]; L.ray.dy = rays[i].dir[1]; L.ray.dz = rays[i].dir[2];
-        }
-        trav8_begin(L, act ? rays[i].tnear : 0.0f, act ? rays[i].tfar : 0.0f);
-        if (!act) L.gbits = 0u;
+        query_begin<Walk8<true>>(L, rays, i, act);
         for (;;) {
             for (;;) {
                 const bool descending = trav8_descending(L);
@@ -296,14 +218,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays8(DScene sc, const RayIO *
         trav8_finish(L);
         if (!act) continue;
         if (occ) occ[i] = L.best.gprim >= 0 ? 1 : 0;
-        else {
-            HitIO o; o.t = 0; o.u = 0; o.v = 0; o.shape_id = -1; o.prim_id = -1;
-            if (L.best.gprim >= 0) {
-                const DPrimShade &ps = sc.prims[L.best.gprim];
-                o.t = L.best.t; o.u = L.best.u; o.v = L.best.v; o.shape_id = ps.shape_id; o.prim_id = ps.prim_id;
-            }
-            hits[i] = o;
-        }
+        else { HitIO o; query_hit(sc, L.best, o); hits[i] = o; }
     }
 }
 

@@ -1,21 +1,14 @@
-// gfx950 kernels of the wavefront integrator.  Written for wave64 / 256-thread workgroups / 160 KB LDS per CU.
+// gfx950 kernels of the wavefront integrator: everything but the ray casts (k_extend: extend.hip, k_extend8: extend8.hip).
+// Written for wave64 / 256-thread workgroups / 160 KB LDS per CU.
 //
-//   k_extend    persistent   : closest hit of the extension ray + any hit of the pending shadow ray over the
-//                              flattened BVH4.  Persistent waves draw 256-slot chunks of live paths from the list the
-//                              preceding shade launch left; a lane whose rays are done pulls the next path instead of
-//                              idling until the slowest lane of the wave finishes (while-while traversal with dynamic
-//                              refill).  Top of the tree, leaf primitives of small scenes and the per-lane traversal
-//                              stacks live in LDS.  (intersection.cpp:7-85)
 //   k_shade     block/segment: hit accounting, NEE, BSDF sampling, Russian roulette (path_tracing.h:58-322).  Each
 //                              workgroup owns one segment of the queue: survivors are compacted to the front of the
 //                              segment in order (wave ballots + a 4-entry LDS scan), then the workgroup's next camera
 //                              samples (path_tracing.h:10-14) are appended behind them and its live chunks listed.
 //                              Instantiated per scene feature set (ShadeFeat).
-//   k_tail      block/segment: the end of a render, fused: trace + shade + compact in a loop inside one launch
+//   k_tail      block/segment: the end of a render, fused: trace (lane by lane, dtrav.h) + shade + compact in a loop inside one launch
 //   k_resolve   wave/pixel   : fixed-order sum of the per-sample radiance -> radiance / spp (render.cpp:94)
-//   k_aux                    : the five auxiliary buffers (render.cpp:12-69)
-//   k_volpath   lane/sample  : the volumetric path tracer (vol_path_tracing.h:503-869), one whole path per lane
-//   k_trace_rays             : batched intersect()/occluded() for the parity tests
+// (k_aux and k_trace_rays: extend.hip; k_volpath, the volumetric path tracer: volpath.hip)
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <algorithm>
@@ -45,144 +38,6 @@ __device__ __forceinline__ void q_store(const DQueue &q, uint32_t i, const PathS
     q.rl[i] = mk4(ps.rad.x, ps.rad.y, ps.rad.z, ps.eta_scale);
     q.rn[i] = mk4(ps.nee.x, ps.nee.y, ps.nee.z, ps.spread);
     q.rg[i] = mk4(u2f(ps.sample), u2f((uint32_t)ps.rng), u2f((uint32_t)(ps.rng >> 32)), ps.p2);
-}
-
-// ---------------------------------------------------------------- extend (the traversal steps live in dtrav.h)
-// STATS: developer instrumentation (LJ_EXTEND_STATS=1): wave-level step counts and the lanes active in them, summed into
-// stats[0..7] = {outer iterations, sum of busy lanes, node steps, lanes in node steps, leaf prim rounds, lanes in them,
-// refills, rays}.  The production instantiation carries none of it.
-#ifndef LJ_EXT_RESIDENT_OCC
-#define LJ_EXT_RESIDENT_OCC 4
-#endif
-template <bool STATS, bool RESIDENT, bool SPHERES>
-#ifndef LJ_EXT_GENERAL_OCC
-#define LJ_EXT_GENERAL_OCC 4
-#endif
-__global__ void __launch_bounds__(kBlock, (RESIDENT && !SPHERES && !STATS) ? LJ_EXT_RESIDENT_OCC : (STATS ? 4 : LJ_EXT_GENERAL_OCC)) k_extend(DScene sc, DQueue q, const DBlockState *blocks, uint32_t seg, uint32_t *work, const uint32_t *chunk_list, uint32_t parity, int stack, int lds_nodes, int lds_prims, int *spill, uint32_t refill_min, uint32_t min_descending, unsigned long long *stats, uint32_t pool_at) {
-    unsigned long long st_outer = 0, st_busy = 0, st_nodes = 0, st_node_lanes = 0, st_leaf = 0, st_leaf_lanes = 0, st_refill = 0, st_rays = 0;
-    const TreeView tv = stage_tree(sc, stack, lds_nodes, lds_prims, spill, gridDim.x * kBlock, blockIdx.x * kBlock + threadIdx.x);
-#if LJ_EXT_POOL
-    const LeafPool lp = leaf_pool_at(pool_at);
-#endif
-    // Persistent waves: the shade launch before this one listed the chunks (kChunk queue slots inside one of its
-    // segments) that hold live paths.  Wave w starts with list entry w; if the list is longer than the grid has
-    // waves, the rest is drawn from one grid-wide counter (which the shade launch preset to the number of waves), so
-    // the launch stays balanced whatever the rays cost.  A launch over a short list issues no atomic at all — a
-    // single address takes only ~90 atomics per microsecond, which would otherwise put a ~50 us floor under every
-    // launch of the render's long tail.  work[0] = draw counter, work[1 + parity] = length of this step's list.
-    const uint32_t n_chunks = work[1 + parity];
-    if (blockIdx.x == 0 && threadIdx.x == 0) work[1 + (parity ^ 1u)] = 0u;   // the next shade launch appends to the other list
-    uint32_t *chunk_counter = work;
-    const bool leader = (threadIdx.x & 63u) == 0u;
-    const uint32_t n_waves = gridDim.x * (kBlock / 64u);
-    const bool draw = n_chunks > n_waves;   // uniform over the grid
-    uint32_t pre = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6);   // next list position (valid in the wave's first lane)
-    uint32_t next = 0, end = 0;             // live slots of the open chunk (wave-uniform)
-    bool exhausted = false;
-    // per-lane state: phase 0 = shadow ray (any hit), phase 1 = extension ray (closest hit)
-    // `start`: the ray this lane has to set up before it traverses again — 1 = its pending shadow ray, 2 = its extension
-    // ray; written by the refill (a new path) and by the end of a shadow ray, consumed at ONE place, so that the ray set-up
-    // code exists once and the traversal state is rewritten in one region of the loop only
-    bool busy = false; int phase = 0; uint32_t path = 0; uint32_t flags = 0; int vis = 0; int start = 0;
-    float edx = 0, edy = 0, edz = 0;
-    LaneTrav L; L.cur = kDone; L.sp = 0; L.held = 0;
-    for (;;) {
-        if (next == end && !exhausted) {    // open the prefetched chunk and draw the one after it
-            const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)pre);
-            if (c >= n_chunks) exhausted = true;
-            else {
-                const uint32_t slot0 = chunk_list[c] * kChunk, b = slot0 / seg, off = slot0 - b * seg, cnt = blocks[b].count;
-                const uint32_t live = cnt > off ? (cnt - off < kChunk ? cnt - off : kChunk) : 0u;
-                next = slot0; end = slot0 + live;
-                if (draw) { if (leader) pre = atomicAdd(chunk_counter, 1u); }
-                else pre = 0xffffffffu;
-                if (live == 0u) continue;
-            }
-        }
-        // ---- refill: lanes without a ray take the next paths of the chunk (kept wave-complete: no early exits above)
-        const unsigned long long idle = __ballot(!busy);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        const uint32_t left = end - next;
-        if (left > 0 && (n_idle >= refill_min || n_idle == 64u)) {
-            if (STATS) st_refill++;
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-            const bool take = !busy && rank < left;
-            if (take) {
-                path = next + rank;
-                const Rec4 ro = q.ro[path], rd = q.rd[path];
-                L.ray.ox = ro.x; L.ray.oy = ro.y; L.ray.oz = ro.z;
-                edx = rd.x; edy = rd.y; edz = rd.z; flags = f2u(rd.w);
-                vis = 0; busy = true;
-                if (ro.w > 0.0f) {  // pending NEE shadow ray [eps, tfar] (path_tracing.h:124-128)
-                    const Rec4 rs = q.rs[path];
-                    L.ray.dx = rs.x; L.ray.dy = rs.y; L.ray.dz = rs.z; L.ray.tfar = ro.w;
-                    start = 1;
-                } else if (!(flags & PF_NO_EXT)) start = 2;
-                else { q.rh[path] = mk4(0.0f, 0.0f, 0.0f, u2f(0u)); busy = false; }
-            }
-            next += n_idle < left ? n_idle : left;
-        }
-        if (start != 0) {
-            // shadow ray [eps, tfar]; extension ray [eps, inf), camera rays from 0 (camera.cpp:46, path_tracing.h:236)
-            const bool ext = start == 2;
-            if (ext) { L.ray.dx = edx; L.ray.dy = edy; L.ray.dz = edz; }
-            trav_begin(L, (ext && (flags & 0xffffu) == 2u) ? 0.0f : sc.eps, ext ? INFINITY : L.ray.tfar);
-            phase = ext ? 1 : 0; start = 0;
-        }
-        if (__ballot(busy) == 0ull) { if (exhausted && next == end) break; else continue; }
-        if (STATS) { st_outer++; st_busy += __popcll(__ballot(busy)); }
-        // ---- while-while traversal: descend inner nodes until every busy lane sits on a leaf (or is done) ...
-        // (lanes that reach a leaf wait here; once only a few lanes are still descending, everybody moves on to the
-        // leaf phase and the stragglers resume in the next round)
-        for (;;) {
-#if LJ_EXT_HOLD && LJ_EXT_POOL
-            if (busy && L.cur < 0 && L.held == 0 && (LJ_EXT_HOLD_SHADOW || phase != 0)) trav_hold<RESIDENT>(tv, L);
-#endif
-            const bool descending = busy && L.cur >= 0 && L.cur != kDone;
-            const unsigned long long dm = __ballot(descending);
-            if (dm == 0ull) break;
-            // only hand over to the leaf phase if some lane actually has a leaf to test (otherwise no progress is made)
-            if ((uint32_t)__popcll(dm) < min_descending && __ballot(busy && (L.cur < 0 || L.held != 0)) != 0ull) break;
-            if (STATS) { st_nodes++; st_node_lanes += __popcll(dm); }
-            if (descending) trav_node_step<RESIDENT>(tv, L);
-        }
-#if LJ_EXT_POOL
-        // ... then the wave tests the primitives of all those leaves together, 64 (ray, primitive) pairs at a time
-        {
-            uint32_t n_pairs;
-            const uint32_t rounds = trav_leaf_pool<RESIDENT, SPHERES>(tv, lp, L, busy && (L.cur < 0 || L.held != 0), phase == 0, n_pairs);
-            if (STATS) { st_leaf += rounds; st_leaf_lanes += n_pairs; }
-        }
-#else
-        if (STATS) {
-            const bool at_leaf = busy && L.cur < 0;
-            int cnt = at_leaf ? ((~L.cur) & 7) + 1 : 0, mx = cnt, sum = cnt;
-            for (int o = 32; o > 0; o >>= 1) { mx = max(mx, __shfl_xor(mx, o, 64)); sum += __shfl_xor(sum, o, 64); }
-            st_leaf += mx; st_leaf_lanes += sum;
-        }
-        // ... then all of them test their leaf together
-        if (busy && L.cur < 0) trav_leaf_step<RESIDENT, SPHERES>(tv, L, phase == 0);
-#endif
-        // ---- ray finished?
-        if (STATS) st_rays += __popcll(__ballot(busy && L.cur == kDone));
-        if (busy && L.cur == kDone) {
-            if (phase == 0) {
-                vis = (L.best.gprim < 0) ? HIT_VIS_BIT : 0;
-                if (!(flags & PF_NO_EXT)) { start = 2; L.cur = 0; }   // (cur leaves kDone here: this block must not run twice)
-                else { q.rh[path] = mk4(0.0f, 0.0f, 0.0f, u2f((uint32_t)vis)); busy = false; }
-            } else {
-                const uint32_t code = (uint32_t)vis | (uint32_t)(L.best.gprim + 1);
-                const bool hit = L.best.gprim >= 0;
-                trav_finish(L);
-                q.rh[path] = mk4(hit ? L.best.t : 0.0f, L.best.u, L.best.v, u2f(code));
-                busy = false;
-            }
-        }
-    }
-    if (STATS && (threadIdx.x & 63) == 0) {
-        atomicAdd(&stats[0], st_outer); atomicAdd(&stats[1], st_busy); atomicAdd(&stats[2], st_nodes); atomicAdd(&stats[3], st_node_lanes);
-        atomicAdd(&stats[4], st_leaf); atomicAdd(&stats[5], st_leaf_lanes); atomicAdd(&stats[6], st_refill); atomicAdd(&stats[7], st_rays);
-    }
 }
 
 // ---------------------------------------------------------------- shade + compaction
@@ -465,19 +320,13 @@ __global__ void __launch_bounds__(kBlock, 2) k_tail(DScene sc, DPass pass, DQueu
                 const Rec4 rs = q.rs[path];
                 L.ray.dx = rs.x; L.ray.dy = rs.y; L.ray.dz = rs.z;
                 trav_begin(L, sc.eps, ro.w);
-                while (L.cur != kDone) {
-                    while (L.cur >= 0 && L.cur != kDone) trav_node_step<false>(tv, L);
-                    if (L.cur < 0) trav_leaf_step<false, true>(tv, L, true);
-                }
+                trace_lane(tv, L, true);
                 vis = (L.best.gprim < 0) ? (uint32_t)HIT_VIS_BIT : 0u;
             }
             if (!(flags & PF_NO_EXT)) {
                 L.ray.dx = rd.x; L.ray.dy = rd.y; L.ray.dz = rd.z;
                 trav_begin(L, ((flags & 0xffffu) == 2u) ? 0.0f : sc.eps, INFINITY);
-                while (L.cur != kDone) {
-                    while (L.cur >= 0 && L.cur != kDone) trav_node_step<false>(tv, L);
-                    if (L.cur < 0) trav_leaf_step<false, true>(tv, L, false);
-                }
+                trace_lane(tv, L, false);
                 trav_finish(L);
                 const bool hit = L.best.gprim >= 0;
                 q.rh[path] = mk4(hit ? L.best.t : 0.0f, L.best.u, L.best.v, u2f(vis | (uint32_t)(L.best.gprim + 1)));
@@ -520,164 +369,7 @@ __global__ void __launch_bounds__(kBlock) k_resolve(DPass pass, uint32_t n_pixel
     }
 }
 
-// ---------------------------------------------------------------- batched ray queries for the parity tests
-
-// Closest hit (or any hit) of every lane's ray, the whole wave together, with k_extend's two phases — inner nodes lane by lane while enough
-// lanes descend, leaves pooled.  L: set up by trav_begin (lanes without a ray: L.cur = kDone).  Ends with trav_finish.
-__device__ __forceinline__ void trace_wave(const TreeView &tv, const LeafPool &lp, LaneTrav &L, const bool any_hit) {
-#if LJ_EXT_POOL
-    for (;;) {
-        for (;;) {
-#if LJ_EXT_HOLD && LJ_EXT_POOL
-            if (L.cur < 0 && L.held == 0) trav_hold<false>(tv, L);
-#endif
-            const bool descending = L.cur >= 0 && L.cur != kDone;
-            if (__ballot(descending) == 0ull) break;
-            if (descending) trav_node_step<false>(tv, L);
-        }
-        const bool at_leaf = L.cur < 0 || L.held != 0;
-        if (__ballot(at_leaf) == 0ull) break;
-        uint32_t n_pairs;
-        (void)trav_leaf_pool<false, true>(tv, lp, L, at_leaf, any_hit, n_pairs);
-    }
-#else
-    while (L.cur != kDone) {
-        while (L.cur >= 0 && L.cur != kDone) trav_node_step<false>(tv, L);
-        if (L.cur < 0) trav_leaf_step<false, true>(tv, L, any_hit);
-    }
-#endif
-    trav_finish(L);
-}
-
-// (wave-complete iterations over the rays, traced by trace_wave: the parity tests of intersect() / occluded() hold the pooled leaf phase
-// to the oracle, bit for bit)
-__global__ void __launch_bounds__(kBlock) k_trace_rays(DScene sc, const RayIO *rays, long long n, HitIO *hits, unsigned char *occ, int stack, int lds_nodes, int lds_prims, int *spill, uint32_t pool_at) {
-    const TreeView tv = stage_tree(sc, stack, lds_nodes, lds_prims, spill, gridDim.x * kBlock, blockIdx.x * kBlock + threadIdx.x);
-    LeafPool lp{};
-#if LJ_EXT_POOL
-    lp = leaf_pool_at(pool_at);
-#endif
-    for (long long i0 = (long long)blockIdx.x * kBlock; i0 < n; i0 += (long long)gridDim.x * kBlock) {
-        const long long i = i0 + threadIdx.x;
-        const bool act = i < n;
-        LaneTrav L;
-        L.ray.ox = 0.0f; L.ray.oy = 0.0f; L.ray.oz = 0.0f; L.ray.dx = 0.0f; L.ray.dy = 0.0f; L.ray.dz = 1.0f;
-        if (act) {
-            L.ray.ox = rays[i].org[0]; L.ray.oy = rays[i].org[1]; L.ray.oz = rays[i].org[2];
-            L.ray.dx = rays[i].dir[0]; L.ray.dy = rays[i].dir[1]; L.ray.dz = rays[i].dir[2];
-        }
-        trav_begin(L, act ? rays[i].tnear : 0.0f, act ? rays[i].tfar : 0.0f);
-        if (!act) L.cur = kDone;
-        trace_wave(tv, lp, L, occ != nullptr);
-        if (!act) continue;
-        if (occ) occ[i] = L.best.gprim >= 0 ? 1 : 0;
-        else {
-            HitIO o; o.t = 0; o.u = 0; o.v = 0; o.shape_id = -1; o.prim_id = -1;
-            if (L.best.gprim >= 0) {
-                const DPrimShade &ps = sc.prims[L.best.gprim];
-                o.t = L.best.t; o.u = L.best.u; o.v = L.best.v; o.shape_id = ps.shape_id; o.prim_id = ps.prim_id;
-            }
-            hits[i] = o;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- auxiliary buffers (render.cpp:12-69)
-// One thread per listed pixel: primary ray through the pixel centre, closest hit, aux_value().
-// (pass: the pixel list, and for a batch of cameras — VIEWS — the table the list's entries are decoded with; no sample buffer, nothing is drawn)
-template <bool VIEWS>
-__global__ void __launch_bounds__(kBlock) k_aux(DScene sc, DPass pass, uint32_t n_pixels, int integrator, float *rgb, int stack, int lds_nodes, int lds_prims, int *spill) {
-    const TreeView tv = stage_tree(sc, stack, lds_nodes, lds_prims, spill, gridDim.x * kBlock, blockIdx.x * kBlock + threadIdx.x);
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_pixels; i += gridDim.x * kBlock) {
-        const uint32_t pixel = pass.pixel_list[i];
-        f3 org, dir;
-        if constexpr (VIEWS) {
-            const ViewPixel vp = view_decode(pass, pixel);
-            with_view_camera(pass, vp.view, [&](const DCamera &cam) { org = ld3(cam.org); dir = camera_primary_dir(cam, vp.x, vp.y, 0.5f, 0.5f); return 0; });
-        } else {
-            const int x = (int)(pixel % (uint32_t)sc.cam.width), y = (int)(pixel / (uint32_t)sc.cam.width);
-            org = ld3(sc.cam.org); dir = camera_primary_dir(sc.cam, x, y, 0.5f, 0.5f);
-        }
-        LaneTrav L;
-        L.ray.ox = org.x; L.ray.oy = org.y; L.ray.oz = org.z; L.ray.dx = dir.x; L.ray.dy = dir.y; L.ray.dz = dir.z;
-        trav_begin(L, 0.0f, INFINITY);   // camera.cpp:46: tnear 0
-        while (L.cur != kDone) {
-            while (L.cur >= 0 && L.cur != kDone) trav_node_step<false>(tv, L);
-            if (L.cur < 0) trav_leaf_step<false, true>(tv, L, false);
-        }
-        trav_finish(L);
-        const f3 c = aux_value(sc, integrator, org, dir, L.best.t, L.best.u, L.best.v, L.best.gprim);
-        rgb[3ull * pixel] = c.x; rgb[3ull * pixel + 1] = c.y; rgb[3ull * pixel + 2] = c.z;
-    }
-}
-
-// ---------------------------------------------------------------- launchers (called from api_device.hip)
-// A traversal of a BVH4 with `depth` inner levels holds at most 3 * depth entries.  The first `stack` levels of every
-// lane's stack live in LDS (1 KiB per level and workgroup); deeper levels — rare — go to a global overflow buffer.
-// LDS per 256-thread workgroup = stack * 1 KiB + staged nodes * 112 B + staged prims * 48 B; four workgroups share a
-// CU's 160 KiB, so the budget per workgroup is 40 KiB.
-
-ExtendConfig extend_config(int n_nodes, int n_prims, int bvh_depth, int n_spheres, int n_nodes8, int bvh8_depth, bool open_scene) {
-    ExtendConfig c{};
-    c.spheres = n_spheres > 0 ? 1 : 0;
-    const int need = 3 * (bvh_depth < 1 ? 1 : bvh_depth);
-    // LDS image: small scenes (which may become fully resident) get 16 stack levels and up to 40 KiB; for the others 12
-    // levels + 20 KiB (the top ~70 nodes): with the 10 KiB of leaf pools a workgroup then takes 30 KiB and five fit a CU (the kernel
-    // needs 92 VGPRs: five waves per SIMD).  tools/lds_sweep.sh, 64 spp: disney_bsdf 28.5 ms at 20-22 KiB against 29.8 at 24 (four
-    // workgroups), sponza flat (63.5 / 63.8); 14 KiB: +2 %; 64 KiB: +30 % — it crowds out the other workgroups of the CU
-    int cap = n_prims <= 256 ? 16 : 12, kib = n_prims <= 256 ? (LJ_EXT_POOL ? 32 : 40) : 20;
-    if (const char *e = getenv("LJ_TUNE_EXT_STACK")) cap = atoi(e);
-    if (const char *e = getenv("LJ_TUNE_EXT_LDS_KB")) kib = atoi(e);
-    c.stack = need < cap ? need : cap;
-    c.spill_levels = need - c.stack;
-    const int budget = kib * 1024 - 256 - c.stack * kBlock * 4;
-    const int small = n_prims <= 256;                                     // primitives only when the whole scene fits (<= 12 KiB)
-    c.lds_prims = small ? n_prims : 0;
-    int max_nodes = (budget - c.lds_prims * 48) / 112;
-    if (max_nodes < 0) max_nodes = 0;
-    c.lds_nodes = n_nodes < max_nodes ? n_nodes : max_nodes;
-    if (!LJ_EXT_LDS_NODES && c.lds_nodes < n_nodes) c.lds_nodes = 0;
-    // whole tree, all primitives and every stack level (+1: the branch-free pushes store one slot ahead) in LDS
-    c.resident = (c.lds_nodes == n_nodes && c.lds_prims == n_prims && c.spill_levels == 0 && c.stack + 1 <= 16) ? 1 : 0;
-    if (c.resident) c.stack += 1;
-    c.smem = (size_t)c.stack * kBlock * 4 + (size_t)c.lds_nodes * 112 + (size_t)c.lds_prims * 48;
-    // tuned on MI355X (tools/pool_probe.sh): when the tree is LDS-resident a node step is cheap and waiting for the last
-    // descending lane costs little; with nodes in L2 the (pooled) leaf phase starts once fewer than 32 lanes still descend
-    // (sponza / disney_bsdf at 64 spp: 16: 65.2 / 30.6 ms, 24: 64.2 / 30.0, 32: 63.2 / 29.7, 40: 63.3 / 30.3, 48: 67.8 / 31.9; with held
-    // leaves — a lane that reaches a leaf keeps descending until its second one — 24: 62.6 / 27.8, 32: 61.7 / 27.5, 40: 60.9 / 27.4)
-    c.refill_min = 8; c.min_descending = (n_nodes <= c.lds_nodes) ? 1 : (LJ_EXT_POOL ? (LJ_EXT_HOLD ? 40 : 32) : 24);
-    // A tree beyond the LDS image can be traversed as a BVH8 instead (k_extend8, extend8.hip): 8-byte group entries, at most one push per
-    // step, 80-byte nodes.  Measured on MI355X (tools/bvh8_ab.sh, tools/ab1024.sh, profiles/r03_bvh8_ab.txt): 26 % fewer node steps per ray
-    // and a third fewer vector-memory instructions, but 26 % more VALU instructions (eight quantised children cost ~200 per step), and with
-    // five waves per SIMD the extend kernel is bound by instruction issue, not by the gather path.  Which tree wins depends on what the rays
-    // do.  In a closed scene every ray ends on a surface and the BVH4's distance-sorted descent culls most of what lies behind it: sponza
-    // 1024 spp 784 ms (BVH4) against 815.  In an open scene under an environment map most rays leave the scene — a ray that hits nothing
-    // visits everything along its way whatever the order, so the BVH8's fewer steps are all gain: disney_bsdf 256 spp 82.5 ms against 85.3,
-    // matpreview 64 spp 61.0 against 65.3, disney_metal 25.3 against 26.4.  So: BVH8 for trees beyond the LDS image of scenes lit by an
-    // environment map, BVH4 otherwise; LJ_TUNE_BVH8=0 / 1 overrides.
-    // A ray's stack is rarely more than four groups deep (sponza: 1 push in 600 lands on level 4, 1 in 10^5 on level 6), so six levels
-    // live in LDS and the rest of the tree's depth goes to the global overflow buffer; with the first 96 nodes (three full levels and part
-    // of the fourth) and the pools a workgroup takes 29.5 KiB: five per CU.  `spill_levels` counts 4-byte units per lane (ensure_spill):
-    // two per group level.
-    const bool can_wide = !c.resident && n_nodes > c.lds_nodes && n_nodes8 > 0;
-    c.wide = (can_wide && open_scene) ? 1 : 0;
-    if (const char *e = getenv("LJ_TUNE_BVH8")) c.wide = (atoi(e) != 0 && can_wide) ? 1 : 0;
-    if (c.wide) {
-        int cap8 = 6, nodes8 = 96;
-        if (const char *e = getenv("LJ_TUNE_EXT8_STACK")) cap8 = atoi(e);
-        if (const char *e = getenv("LJ_TUNE_EXT8_NODES")) nodes8 = atoi(e);
-        const int need8 = bvh8_depth < 1 ? 1 : bvh8_depth;
-        c.stack8 = need8 < cap8 ? need8 : cap8;
-        if (c.stack8 < 1) c.stack8 = 1;
-        c.lds_nodes8 = n_nodes8 < nodes8 ? n_nodes8 : nodes8;
-        c.smem8 = (size_t)c.stack8 * kBlock * 8 + (size_t)c.lds_nodes8 * 80;
-        const int spill8 = 2 * (need8 - c.stack8 > 0 ? need8 - c.stack8 : 0);
-        if (spill8 > c.spill_levels) c.spill_levels = spill8;   // (k_aux / k_volpath still walk the BVH4 with the 4-byte levels)
-    }
-    return c;
-}
-int max_stack_depth() { return 40; }  // inner levels; the builder's own cap is 38
-
+// ---------------------------------------------------------------- launchers (called from render.hip)
 // LDS staging plan of the shade kernel; sizes are rounded up to 16 bytes (the device buffers are padded accordingly).
 ShadeConfig shade_config(size_t n_prims, size_t n_materials, size_t n_lights, size_t n_light_tris, size_t n_light_tri_cdf, size_t n_images3, size_t n_images1, size_t n_env_marg) {
     auto r16 = [](size_t b) { return (uint32_t)((b + 15) & ~(size_t)15); };
@@ -703,26 +395,6 @@ ShadeConfig shade_config(size_t n_prims, size_t n_materials, size_t n_lights, si
     return c;
 }
 
-// LDS of an extend launch: the traversal image, then the leaf pools of its four waves
-size_t extend_smem(const ExtendConfig &cfg) { return ((cfg.smem + 15) & ~(size_t)15) + (LJ_EXT_POOL ? (kBlock / 64) * kWavePoolBytes : 0); }
-void launch_extend(const DScene &sc, const DQueue &q, const DBlockState *blocks, uint32_t grid, uint32_t seg, uint32_t *work, const uint32_t *chunk_list, uint32_t parity, const ExtendConfig &cfg, int *spill, unsigned long long *stats, hipStream_t s) {
-    if (cfg.wide) { launch_extend8(sc, q, blocks, grid, seg, work, chunk_list, parity, cfg, spill, stats, s); return; }
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), extend_smem(cfg), s, sc, q, blocks, seg, work, chunk_list, parity, cfg.stack, cfg.lds_nodes, cfg.lds_prims, spill, cfg.refill_min, cfg.min_descending, stats,
-                           (uint32_t)((cfg.smem + 15) & ~(size_t)15));
-    };
-    const int variant = (stats ? 4 : 0) | (cfg.resident ? 2 : 0) | (cfg.spheres ? 1 : 0);
-    switch (variant) {
-        case 0: launch(k_extend<false, false, false>); break;
-        case 1: launch(k_extend<false, false, true>); break;
-        case 2: launch(k_extend<false, true, false>); break;
-        case 3: launch(k_extend<false, true, true>); break;
-        case 4: launch(k_extend<true, false, false>); break;
-        case 5: launch(k_extend<true, false, true>); break;
-        case 6: launch(k_extend<true, true, false>); break;
-        default: launch(k_extend<true, true, true>); break;
-    }
-}
 // shade_variant() returns the first (smallest) feature set that covers a scene
 int shade_variant(uint32_t kinds, bool textured, bool envmap, bool sphere_lights) {
     for (int v = 0; v < kNumShadeVariants; v++) if (variant_covers(v, kinds, textured, envmap, sphere_lights)) return v;
@@ -767,13 +439,6 @@ void launch_resolve(const DPass &pass, uint32_t n_pixels, float *rgb, hipStream_
     const uint32_t waves_per_block = kBlock / 64;
     const uint32_t grid = (n_pixels + waves_per_block - 1) / waves_per_block;
     if (grid) hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(kBlock), 0, s, pass, n_pixels, rgb);
-}
-void launch_aux(const DScene &sc, const DPass &pass, uint32_t n_pixels, int integrator, float *rgb, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s) {
-    if (n_pixels) hipLaunchKernelGGL(pass.views ? k_aux<true> : k_aux<false>, dim3(grid), dim3(kBlock), cfg.smem, s, sc, pass, n_pixels, integrator, rgb, cfg.stack, cfg.lds_nodes, cfg.lds_prims, spill);
-}
-void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s) {
-    if (cfg.wide) { launch_trace_rays8(sc, rays, n, hits, occ, cfg, spill, grid, s); return; }
-    hipLaunchKernelGGL(k_trace_rays, dim3(grid), dim3(kBlock), extend_smem(cfg), s, sc, (const RayIO *)rays, n, (HitIO *)hits, occ, cfg.stack, cfg.lds_nodes, cfg.lds_prims, spill, (uint32_t)((cfg.smem + 15) & ~(size_t)15));
 }
 
 } // namespace ljd

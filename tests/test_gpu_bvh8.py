@@ -42,3 +42,22 @@ def test_bvh8_kernels_match_oracle_and_bvh4(name, ctx, monkeypatch):
     s4 = sc4.stats()
     assert np.array_equal(p8.view(np.uint32), p4.view(np.uint32))
     assert (s8.rays_closest, s8.rays_shadow, s8.bounce_iterations) == (s4.rays_closest, s4.rays_shadow, s4.bounce_iterations)
+
+
+# The LJ_EXTEND_STATS=1 instantiations of both extend kernels (k_extend<true, ...>, k_extend8<true, ...>) count what the wave does and must
+# trace exactly what the production instantiations trace: per-sample radiance with the counters on is bit-identical to the same call
+# without them.  (LJ_EXTEND_STATS and LJ_TUNE_MEGA are read at every render, LJ_TUNE_BVH8 at upload.)
+@pytest.mark.parametrize("name,crop,env", [
+    ("cbox", (240, 300, 272, 332), {"LJ_TUNE_MEGA": "0"}),      # tree, primitives and stacks in LDS: k_extend<true, RESIDENT>
+    ("sponza", CROPS["sponza"], {"LJ_TUNE_BVH8": "0"}),         # BVH4 beyond the LDS image: k_extend<true, false>
+    ("sponza", CROPS["sponza"], {"LJ_TUNE_BVH8": "1"}),         # the same tree eight wide: k_extend8<true, ...>
+], ids=["cbox-resident", "sponza-bvh4", "sponza-bvh8"])
+def test_extend_stats_instantiations_trace_the_same_rays(name, crop, env, ctx, monkeypatch):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    sc = lj.Scene(ctx, lj.parse_scene(scene_path(name)))
+    plain = lj.render_samples(sc, crop, spp=2)
+    monkeypatch.setenv("LJ_EXTEND_STATS", "1")
+    counted = lj.render_samples(sc, crop, spp=2)
+    assert plain.shape == (32, 32, 2, 3) and np.isfinite(plain).all() and plain.max() > 0
+    assert np.array_equal(counted.view(np.uint32), plain.view(np.uint32))
