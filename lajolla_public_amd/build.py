@@ -181,6 +181,22 @@ def build_twin_regen(verbose=True):
     return TWIN_REGEN_LIB
 
 
+TWIN_POOL_LIB = os.path.join(ROOT, "tests", "twin_pool", "_build", "libljtwinpool_asan.so" if _SAN else "libljtwinpool.so")
+
+
+def build_twin_pool(verbose=True):
+    """Host model of one k_mega wave's candidate pool over the kernel's pass arithmetic (device/dmegapool.h) for the CPU-side tests."""
+    src = os.path.join(ROOT, "tests", "twin_pool", "twin_pool.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_POOL_LIB), exist_ok=True)
+    if _stale(TWIN_POOL_LIB, [src] + _headers()):
+        if verbose:
+            print("[build] compiling the host model of the mega kernel's candidate pool (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2"] + _SAN_FLAGS + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", TWIN_POOL_LIB, src])
+    return TWIN_POOL_LIB
+
+
 TWIN_SCAN_LIB = os.path.join(ROOT, "tests", "twin_scan", "_build", "libljtwinscan_asan.so" if _SAN else "libljtwinscan.so")
 
 
@@ -249,6 +265,7 @@ if __name__ == "__main__":
         build_twin()
         build_twin_tile()
         build_twin_regen()
+        build_twin_pool()
         build_twin_scan()
         build_twin_views()
         build_twin_refit()

@@ -306,7 +306,7 @@ static int trace_batch(lj_scene *scene, int64_t n, const LjRay *rays_host, LjHit
         // traversal of k_extend, as for every other scene)
         const bool scan = scene->dscene.n_scan_leaves > 0 && mega_enabled();
         HIP_CHECK(hipEventRecord(ctx->ev_begin, ctx->stream));
-        if (scan) ljd::launch_trace_rays_scan(scene->dscene, rays.p, n, hits_host ? out.p : nullptr, hits_host ? nullptr : (unsigned char *)out.p, grid, ctx->stream);
+        if (scan) ljd::launch_trace_rays_scan(scene->dscene, rays.p, n, hits_host ? out.p : nullptr, hits_host ? nullptr : (unsigned char *)out.p, mega_item_cap_tune(), grid, ctx->stream);
         else ljd::launch_trace_rays(scene->dscene, rays.p, n, hits_host ? out.p : nullptr, hits_host ? nullptr : (unsigned char *)out.p, scene->ecfg, ensure_spill(ctx, scene->ecfg.spill_levels, (uint32_t)grid), grid, ctx->stream);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(ctx->ev_end, ctx->stream));

@@ -35,8 +35,8 @@ void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hi
 // mega.hip
 size_t mega_smem(const DScene &sc, const ShadeConfig &scfg);
 int mega_blocks_per_cu(const DScene &sc, const ShadeConfig &scfg);
-void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, bool spheres, uint32_t n_samples, uint32_t grab, uint32_t *sample_counter, unsigned long long *stats, int grid, hipStream_t s);
-void launch_trace_rays_scan(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, int grid, hipStream_t s);
+void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, bool spheres, uint32_t n_samples, uint32_t grab, uint32_t item_cap_tune, uint32_t *sample_counter, unsigned long long *stats, int grid, hipStream_t s);
+void launch_trace_rays_scan(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, uint32_t item_cap_tune, int grid, hipStream_t s);
 // tile.hip: the per-tile schedule (LJ_RNG_TILE)
 size_t tile_cursor_bytes(bool vol);
 void launch_tile_init(bool vol, void *cursors, const uint32_t *tiles, uint32_t n_tiles, uint64_t seed, hipStream_t s);
@@ -75,6 +75,9 @@ inline int env_int(const char *name, int dflt) {
 }
 // LJ_TUNE_MEGA=0: no scene takes the leaf-scan route of mega.hip — a render runs the wavefront kernels, a ray query k_extend's traversal
 inline bool mega_enabled() { return env_int("LJ_TUNE_MEGA", 1) != 0; }
+// LJ_TUNE_MEGA_ITEM_CAP=n: the leaf scan pools at most n candidates per wave and pass (clamped to [1, the build's pool] by the launchers; 0: unset).
+// Read per render and per query: the tests reach several passes per wave-step with it at sizes where the pool would never fill.
+inline uint32_t mega_item_cap_tune() { return (uint32_t)std::max(0, env_int("LJ_TUNE_MEGA_ITEM_CAP", 0)); }
 
 template <typename T> inline void upload(DevBuf &b, const std::vector<T> &v, hipStream_t s) {
     b.alloc(((std::max<size_t>(v.size(), 1) * sizeof(T)) + 31) & ~(size_t)15);

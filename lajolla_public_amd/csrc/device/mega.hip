@@ -20,12 +20,14 @@
 #include "dconfig.h"
 #include "dregen.h"
 #include "dscan.h"
+#include "dmegapool.h"
 
 namespace ljd {
 
 #define LJ_CONST __attribute__((address_space(4)))   // constant address space: uniform loads become s_load (scalar cache)
 
-// (ray, leaf) candidates pooled per wave and pass: a pass stops taking rounds above the cap - 64, the rest waits for the next pass.  512,
+// (ray, leaf) candidates pooled per wave and pass: a pass lists the wave's first `cap` candidates in lane order (dmegapool.h: the whole cap is
+// used, a lane's candidates may be split between passes), the rest waits for the next pass.  LJ_TUNE_MEGA_ITEM_CAP lowers it per render / query.  512,
 // except in the k_mega build that carries a camera-sample stash (below; cbox: a wave-step pools ~150, 2.3 per lane): 304 there, so that
 // its workgroup needs 31 984 B of LDS — the most that still lets five of them share a CU (kLdsPerCU in kLdsGranule steps: 32 000 B each).
 constexpr uint32_t kItemCap = 512, kItemCapTight = 304;
@@ -53,6 +55,19 @@ struct ScanCtx {
 };
 
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// Inclusive prefix sum over the 64 lanes of a wave (all of them active), no ballot and no LDS: six DPP adds — within each row of 16 lanes by
+// row_shr 1, 2, 4, 8 (lanes the shift runs out of add 0), then lane 15 of row 0 / 2 into row 1 / 3 (row_bcast:15, row_mask 0xa) and lane 31
+// into rows 2 and 3 (row_bcast:31, row_mask 0xc).  Lane 63 holds the wave's total.
+__device__ __forceinline__ uint32_t wave_prefix_incl(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+    return v;
+}
 
 // Leaf-box scan: one bit of a ray's mask per leaf box its segment [tnear, tfar] overlaps.  Slab arithmetic on the table's centre /
 // half-extent records (dscan.h: scan_box with its error argument, the 1e-18 clamp of tiny direction components; exit widened by 4 ulp;
@@ -106,7 +121,9 @@ __device__ __forceinline__ void scan_leaf_boxes2(const ScanCtx &sx, f3 org, f3 d
 
 // Closest hit of every lane's extension ray (has_e) and occlusion of its shadow ray (has_s), wave-synchronous: all 64 lanes
 // call it together.  Results: gprim (-1: miss), t, u, v exactly as k_extend reports them; occluded.
-template <bool SPHERES>
+// LANE_MAJOR: how the candidates are listed (mega_pool_lane_major below) — the order cannot change a result: the closest hit is a minimum
+// over a total order and occlusion an OR.
+template <bool SPHERES, bool LANE_MAJOR>
 __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool has_s, f3 org, f3 dir_e, float tnear_e, f3 dir_s, float tnear_s, float tfar_s,
                                            float &ht, float &hu, float &hv, int &gprim_out, bool &occluded) {
     // No floating-point contraction in here: u = U * (1 / S) must reach the shading code as the rounded product k_extend stores in
@@ -123,28 +140,43 @@ __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool h
     sx.rays[lane * 3] = r0; sx.rays[lane * 3 + 1] = r1; sx.rays[lane * 3 + 2] = r2;
     sx.keys[lane] = ~0ull; sx.occl[lane] = 0;
     for (;;) {
-        // ---- pool the candidates of all lanes: round j takes every lane's j-th candidate (shadow ray first)
-        uint32_t n_items = 0;
-        for (;;) {
-            const bool has = (ms | me) != 0u;
-            const unsigned long long b = __ballot(has);
-            if (b == 0ull || n_items + 64u > sx.item_cap) break;
-            if (has) {
-                uint32_t leaf, kind;
-                if (ms) { leaf = (uint32_t)(sx.n_used - 1) - (uint32_t)__builtin_ctz(ms); ms &= ms - 1u; kind = 1u; }
-                else { leaf = (uint32_t)(sx.n_used - 1) - (uint32_t)__builtin_ctz(me); me &= me - 1u; kind = 0u; }
-                const uint32_t idx = n_items + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-                sx.items[idx] = (uint16_t)(lane | (leaf << 6) | (kind << 11));
+        uint32_t n_items = 0, total = 0;
+        if constexpr (LANE_MAJOR) {
+            // ---- pool the candidates of all lanes, lane-major: one prefix sum over the lanes' counts, then every lane lists its own (shadow ray
+            // first) from the index the sum gives it — as many as the pool still holds there (pool_share: no index reaches items[item_cap])
+            const uint32_t c_s = (uint32_t)__builtin_popcount(ms), c = c_s + (uint32_t)__builtin_popcount(me), incl = wave_prefix_incl(c);
+            total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            if (total == 0u) break;
+            uint32_t n_s, n_e, idx = incl - c;
+            pool_share(c_s, c - c_s, idx, sx.item_cap, n_s, n_e);
+            for (const uint32_t end = idx + n_s; idx != end; idx++) sx.items[idx] = (uint16_t)pool_item(lane, pool_pop(ms));
+            for (const uint32_t end = idx + n_e; idx != end; idx++) sx.items[idx] = (uint16_t)pool_item(lane, kPoolExtBit + pool_pop(me));
+            n_items = pool_pass_items(total, sx.item_cap);
+        } else {
+            // ---- pool them in rounds: round j takes every lane's j-th candidate (shadow ray first); a pass stops taking rounds above
+            // item_cap - 64 (item_cap >= 64 here: clamp_item_cap).  A test round then holds candidates of one rank: rays that run together
+            // meet the same leaf there, its primitives are read by broadcast and a sphere leaf's lanes do not wait for a triangle leaf's
+            for (;;) {
+                const bool has = (ms | me) != 0u;
+                const unsigned long long b = __ballot(has);
+                if (b == 0ull || n_items + 64u > sx.item_cap) break;
+                if (has) {
+                    uint32_t bit;
+                    if (ms) bit = pool_pop(ms); else bit = kPoolExtBit + pool_pop(me);
+                    const uint32_t idx = n_items + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+                    sx.items[idx] = (uint16_t)pool_item(lane, bit);
+                }
+                n_items += (uint32_t)__popcll(b);
             }
-            n_items += (uint32_t)__popcll(b);
+            if (n_items == 0u) break;
         }
-        if (n_items == 0u) break;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-        // ---- test them, 64 at a time, whichever lane is free
+        // ---- test them, 64 at a time, whichever lane is free (lane-major: consecutive items mostly share a ray, its reads are LDS broadcasts)
         for (uint32_t r = 0; r < n_items; r += 64u) {
-            if (r + lane < n_items) {
-                const uint32_t it = sx.items[r + lane];
-                const uint32_t src = it & 63u, leaf = (it >> 6) & 31u, kind = it >> 11;
+            const uint32_t slot = r + lane;
+            if (slot < n_items) {
+                const uint32_t it = sx.items[slot];
+                const uint32_t src = pool_item_lane(it), leaf = pool_item_leaf(it, (uint32_t)sx.n_used), kind = 1u - pool_item_ext(it);
                 const v4f o4 = sx.rays[src * 3], d4 = sx.rays[src * 3 + 1 + kind];
                 RayF ray;
                 ray.ox = o4.x; ray.oy = o4.y; ray.oz = o4.z; ray.dx = d4.x; ray.dy = d4.y; ray.dz = d4.z;
@@ -172,7 +204,8 @@ __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool h
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-        if (__ballot((ms | me) != 0u) == 0ull) break;
+        if constexpr (LANE_MAJOR) { if (pool_last_pass(total, sx.item_cap)) break; }   // (the next prefix sum would come to 0)
+        else if (__ballot((ms | me) != 0u) == 0ull) break;
     }
     // ---- every lane picks up its own results; the winner's barycentrics are recomputed (one test per ray instead of carrying
     // U, V, S through the pool)
@@ -225,7 +258,7 @@ __device__ __forceinline__ void stash_start(const DScene &sc, const DPass &pass,
 
 // LDS image of the scan area at byte offset `at` (16-byte aligned): [leaf table][primitives, transposed][4 x wave scratch]
 template <uint32_t ITEM_CAP, bool STASH>
-__device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at) {
+__device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at, uint32_t item_cap) {
     ScanCtx sx;
     char *base = (char *)lj_smem + at;
     LJ_LDS int *lt = (LJ_LDS int *)base;
@@ -240,7 +273,8 @@ __device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at) {
     sx.rays = (LJ_LDS v4f *)wave; sx.keys = (LJ_LDS unsigned long long *)(wave + 64 * 48);
     sx.st_rng = (LJ_LDS uint64_t *)(wave + 64 * 48 + 64 * 8); sx.st_dir = (LJ_LDS float *)(wave + 64 * 48 + 64 * 8 + kRegenSlots * 8);
     const uint32_t after = 64 * 48 + 64 * 8 + (STASH ? kWaveStashBytes : 0u);   // (without a stash st_rng / st_dir are never used)
-    sx.occl = (LJ_LDS uint8_t *)(wave + after); sx.items = (LJ_LDS uint16_t *)(wave + after + 64); sx.item_cap = ITEM_CAP;
+    sx.occl = (LJ_LDS uint8_t *)(wave + after); sx.items = (LJ_LDS uint16_t *)(wave + after + 64);
+    sx.item_cap = item_cap < ITEM_CAP ? item_cap : ITEM_CAP;   // (the launchers pass 1 .. ITEM_CAP: the pool is ITEM_CAP items whatever arrives)
     return sx;
 }
 size_t scan_smem(int n_scan_leaves, int n_prims, uint32_t item_cap = kItemCap, bool stash = false) { return (((size_t)n_scan_leaves * 8 + 15) & ~(size_t)15) + (size_t)n_prims * 48 + 4 * (size_t)wave_scan_bytes(item_cap, stash); }
@@ -270,14 +304,20 @@ template <class Ft> constexpr bool mega_stash() { return LJ_MEGA_STASH && MegaOc
 #endif
 template <class Ft> constexpr uint32_t mega_item_cap() { return (mega_stash<Ft>() || (LJ_MEGA_ITEM_CAP_TIGHT && MegaOccupancy<Ft>::waves >= 5)) ? kItemCapTight : kItemCap; }
 
+// Which builds list the scan's candidates lane-major off one wave prefix sum (scan_trace, dmegapool.h) instead of in rounds.  It takes 57 vector
+// and 113 scalar instructions off a cbox wave-step (-3.1 % of a render); on veach_mi (spheres, Plastic build, 26 leaves, coherent rays) a render
+// was 5 % SLOWER with it — a lane-major test round mixes leaves, so sphere and triangle leaves share rounds (profiles/mega_pool_ab.txt).
+// So: the triangle-only five-wave Lambert build, and the ray queries; every other build pools in rounds, as before.
+template <class Ft, bool SPHERES> constexpr bool mega_pool_lane_major() { return !SPHERES && MegaOccupancy<Ft>::waves >= 5; }
+
 // stats: [0] bounce iterations, [1] closest-hit rays, [2] shadow rays, [3] samples finished, [4] path steps (shade_path calls)
 // (VIEWS: the pass is a batch of cameras, dshade.h; same occupancy, same LDS — the stash has no per-view entry)
 template <class Ft, bool SPHERES, bool VIEWS>
 __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScene sc, DPass pass, ShadeStage stg, uint32_t scan_at, uint32_t n_samples, uint32_t grab,
-                                                              uint32_t *sample_counter, unsigned long long *stats) {
+                                                              uint32_t item_cap, uint32_t *sample_counter, unsigned long long *stats) {
     stage_shade_tables<2>(sc, stg, 0u);
     constexpr bool STASH = mega_stash<Ft>();
-    const ScanCtx sx = stage_scan<mega_item_cap<Ft>(), STASH>(sc, scan_at);
+    const ScanCtx sx = stage_scan<mega_item_cap<Ft>(), STASH>(sc, scan_at, item_cap);
     __syncthreads();
     const uint32_t lane = lane_id();
     ShadeCounters cnt; cnt.bounces = cnt.closest = cnt.shadow = cnt.done = 0;
@@ -356,7 +396,7 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
         opaque_state(ps);
         const bool has_e = live && !(ps.flags & PF_NO_EXT), has_s = live && ps.stfar > 0.0f;
         float ht, hu, hv; int gprim; bool occluded;
-        scan_trace<SPHERES>(sx, has_e, has_s, ps.org, ps.dir, (ps.flags & 0xffffu) == 2u ? 0.0f : sc.eps, ps.sdir, sc.eps, ps.stfar, ht, hu, hv, gprim, occluded);
+        scan_trace<SPHERES, mega_pool_lane_major<Ft, SPHERES>()>(sx, has_e, has_s, ps.org, ps.dir, (ps.flags & 0xffffu) == 2u ? 0.0f : sc.eps, ps.sdir, sc.eps, ps.stfar, ht, hu, hv, gprim, occluded);
         if (live) {
             if (has_s && !occluded) ps.rad = add_rounded(ps.rad, ps.nee);   // path_tracing.h:207 (k_shade adds it at the top of the next step)
             ps.ht = ht; ps.hu = hu; ps.hv = hv; ps.hcode = gprim + 1;
@@ -377,8 +417,8 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
 // batched intersect() / occluded() through the scan (the parity tests hold it bit for bit to the oracle like the BVH traversal)
 struct RayIO { float org[3]; float tnear; float dir[3]; float tfar; };
 struct HitIO { float t, u, v; int32_t shape_id, prim_id; };
-__global__ void __launch_bounds__(kBlock) k_trace_rays_scan(DScene sc, const RayIO *rays, long long n, HitIO *hits, unsigned char *occ) {
-    const ScanCtx sx = stage_scan<kItemCap, false>(sc, 0u);
+__global__ void __launch_bounds__(kBlock) k_trace_rays_scan(DScene sc, const RayIO *rays, long long n, HitIO *hits, unsigned char *occ, uint32_t item_cap) {
+    const ScanCtx sx = stage_scan<kItemCap, false>(sc, 0u, item_cap);
     __syncthreads();
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long i0 = (long long)blockIdx.x * kBlock; i0 < n; i0 += stride) {   // wave-complete iterations
@@ -388,11 +428,11 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays_scan(DScene sc, const Ray
         if (act) { org = ld3(rays[i].org); dir = ld3(rays[i].dir); tn = rays[i].tnear; tf = rays[i].tfar; }
         float ht, hu, hv; int gprim; bool occluded;
         if (occ) {   // any hit in (tnear, tfar]: the shadow-ray slot
-            scan_trace<true>(sx, false, act, org, dir, 0.0f, dir, tn, tf, ht, hu, hv, gprim, occluded);
+            scan_trace<true, true>(sx, false, act, org, dir, 0.0f, dir, tn, tf, ht, hu, hv, gprim, occluded);
             if (act) occ[i] = occluded ? 1 : 0;
         } else {
             // closest hit in (tnear, tfar]: the extension-ray slot has tfar = inf, so the far end is applied to the result
-            scan_trace<true>(sx, act, false, org, dir, tn, dir, 0.0f, 0.0f, ht, hu, hv, gprim, occluded);
+            scan_trace<true, true>(sx, act, false, org, dir, tn, dir, 0.0f, 0.0f, ht, hu, hv, gprim, occluded);
             if (act) {
                 HitIO o; o.t = 0; o.u = 0; o.v = 0; o.shape_id = -1; o.prim_id = -1;
                 if (gprim >= 0 && ht <= tf) { const DPrimShade &ps = sc.prims[gprim]; o.t = ht; o.u = hu; o.v = hv; o.shape_id = ps.shape_id; o.prim_id = ps.prim_id; }
@@ -423,22 +463,31 @@ int mega_blocks_per_cu(const DScene &sc, const ShadeConfig &scfg) {
     return waves < by_lds ? waves : by_lds;
 }
 
-void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, bool spheres, uint32_t n_samples, uint32_t grab, uint32_t *sample_counter,
-                 unsigned long long *stats, int grid, hipStream_t s) {
+// the pool's size for one launch: `tune` items (LJ_TUNE_MEGA_ITEM_CAP; 0: unset) within [1, what the build's LDS holds] — [64, that] where
+// the candidates are pooled in rounds of up to 64
+static uint32_t clamp_item_cap(uint32_t tune, uint32_t build_cap, bool lane_major) {
+    const uint32_t lo = lane_major ? 1u : 64u;
+    return tune == 0u || tune > build_cap ? build_cap : (tune < lo ? lo : tune);
+}
+
+void launch_mega(const DScene &sc, const DPass &pass, const ShadeConfig &scfg, bool spheres, uint32_t n_samples, uint32_t grab, uint32_t item_cap_tune,
+                 uint32_t *sample_counter, unsigned long long *stats, int grid, hipStream_t s) {
     const ShadeStage st = make_shade_stage(scfg);
     const uint32_t at = (uint32_t)((scfg.smem + 15) & ~(size_t)15);
     const size_t smem = mega_smem(sc, scfg);
     with_shade_variant(scfg.variant, [&](auto ft) {
         using Ft = decltype(ft);
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), smem, s, sc, pass, st, at, n_samples, grab, sample_counter, stats); };
+        const uint32_t item_cap = clamp_item_cap(item_cap_tune, mega_item_cap<Ft>(), spheres ? mega_pool_lane_major<Ft, true>() : mega_pool_lane_major<Ft, false>());
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), smem, s, sc, pass, st, at, n_samples, grab, item_cap, sample_counter, stats); };
         if (pass.views) { if (spheres) launch(k_mega<Ft, true, true>); else launch(k_mega<Ft, false, true>); }
         else if (spheres) launch(k_mega<Ft, true, false>);
         else launch(k_mega<Ft, false, false>);
     });
 }
 
-void launch_trace_rays_scan(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, int grid, hipStream_t s) {
-    hipLaunchKernelGGL(k_trace_rays_scan, dim3(grid), dim3(kBlock), scan_smem(sc.n_scan_leaves, sc.n_prims), s, sc, (const RayIO *)rays, n, (HitIO *)hits, occ);
+void launch_trace_rays_scan(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, uint32_t item_cap_tune, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_trace_rays_scan, dim3(grid), dim3(kBlock), scan_smem(sc.n_scan_leaves, sc.n_prims), s, sc, (const RayIO *)rays, n, (HitIO *)hits, occ,
+                       clamp_item_cap(item_cap_tune, kItemCap, true));
 }
 
 } // namespace ljd

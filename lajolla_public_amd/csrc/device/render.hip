@@ -201,6 +201,7 @@ void render_mega(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &plan, ui
     const bool grab_fixed = env_set("LJ_TUNE_MEGA_GRAB");
     const uint32_t grab_min = 192, grab_max = grab_fixed ? (uint32_t)std::max(64, env_int("LJ_TUNE_MEGA_GRAB", 768)) & ~63u : 768u;
     const uint64_t draws = (uint64_t)std::max(1, env_int("LJ_TUNE_MEGA_DRAWS", 16));
+    const uint32_t item_cap_tune = mega_item_cap_tune();
     unsigned long long hstats[5] = {};
     for (uint64_t p0 = 0; p0 < plan.pixels->size(); p0 += pix_per_pass) {
         const Pass P = pass_at(sc, plan, p0, pix_per_pass);
@@ -215,7 +216,7 @@ void render_mega(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &plan, ui
         const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx->n_cus * per_cu, (pieces + 3) / 4));
         unsigned long long *stats_dev = (unsigned long long *)((char *)ctx->mega_state.p + 8);
         if (timing) HIP_CHECK(hipEventRecord(ctx->ev_k0, stream));
-        ljd::launch_mega(ds, P.d, sc->scfg, sc->flat.n_spheres > 0, (uint32_t)P.total, grab, (uint32_t *)ctx->mega_state.p, stats_dev, grid, stream);
+        ljd::launch_mega(ds, P.d, sc->scfg, sc->flat.n_spheres > 0, (uint32_t)P.total, grab, item_cap_tune, (uint32_t *)ctx->mega_state.p, stats_dev, grid, stream);
         HIP_CHECK(hipGetLastError());
         if (timing) {
             HIP_CHECK(hipEventRecord(ctx->ev_k1, stream)); HIP_CHECK(hipEventSynchronize(ctx->ev_k1));
