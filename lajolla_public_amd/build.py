@@ -197,6 +197,22 @@ def build_twin_pool(verbose=True):
     return TWIN_POOL_LIB
 
 
+TWIN_ROUND_LIB = os.path.join(ROOT, "tests", "twin_round", "_build", "libljtwinround_asan.so" if _SAN else "libljtwinround.so")
+
+
+def build_twin_round(verbose=True):
+    """Host model of the test rounds of a k_mega pass, the split of a short last round included (device/dmegapool.h), for the CPU-side tests."""
+    src = os.path.join(ROOT, "tests", "twin_round", "twin_round.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_ROUND_LIB), exist_ok=True)
+    if _stale(TWIN_ROUND_LIB, [src] + _headers()):
+        if verbose:
+            print("[build] compiling the host model of the mega kernel's test rounds (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2"] + _SAN_FLAGS + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-o", TWIN_ROUND_LIB, src])
+    return TWIN_ROUND_LIB
+
+
 TWIN_SCAN_LIB = os.path.join(ROOT, "tests", "twin_scan", "_build", "libljtwinscan_asan.so" if _SAN else "libljtwinscan.so")
 
 
@@ -266,6 +282,7 @@ if __name__ == "__main__":
         build_twin_tile()
         build_twin_regen()
         build_twin_pool()
+        build_twin_round()
         build_twin_scan()
         build_twin_views()
         build_twin_refit()

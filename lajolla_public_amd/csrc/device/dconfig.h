@@ -3,7 +3,17 @@
 #include <stddef.h>
 #include <stdint.h>
 
+// LJ_MEGA_ROUND_STATS (a developer build, tools/dev/mega_round_stats.sh): per pass of k_mega's test loop, how many items it held, how many
+// rounds it ran and how full the last of them was — what splitting a short last round by primitive (dmegapool.h) can save.  Three atomics per
+// pass: never on in a build that is timed.  The tallies follow the launch's five statistics (mega.hip: kMegaRoundStats of them); render_mega
+// (render.hip) prints them.
+#ifndef LJ_MEGA_ROUND_STATS
+#define LJ_MEGA_ROUND_STATS 0
+#endif
+
 namespace ljd {
+
+constexpr int kMegaRoundStats = 11;   // [0] passes, [1] items, [2] test rounds, [3 + k] passes whose last round held 8 k + 1 .. 8 k + 8 items
 
 // feature-set instantiations of the shading code (dshade.h lists them, smallest first)
 constexpr int kNumShadeVariants = 6;

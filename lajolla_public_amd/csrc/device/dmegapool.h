@@ -54,4 +54,35 @@ LJ_HD uint32_t pool_pop(uint32_t &m) {
     return bit;
 }
 
+// ---- the short last test round of a pass, split by primitive
+//
+// The test loop walks the pass's items 64 at a time, every lane the `count` primitives of its item's leaf one after the other.  The last round
+// holds m = n_items - r items; when that is few enough, several lanes share an item.  With M the largest `count` of the leaf table rounded up
+// to a power of two (a scene constant, wave-uniform), a round of m * M <= 64 items runs ONE primitive per lane: lane l takes primitive l % M
+// of item r + l / M, and is idle when that item does not exist or its leaf has no such primitive.  M = 1 never splits: there is nothing to
+// share out.  A table whose largest leaf is an exception (cbox: seventeen leaves of two triangles and one of four, so M = 4) would split
+// only below 64 / M items; so a round too long for M lanes per item takes the widest power of two W < M with m * W <= 64 instead: lane l
+// then walks primitives l % W, l % W + W, ... of item r + l / W.  W = M is the case above, W = 1 the unsplit round.  The order of the tests
+// cannot change a result (closest hit: a minimum over a total order; occlusion: an OR).
+
+// M of a leaf table whose largest leaf holds max_count primitives (1 for an empty table)
+LJ_HD uint32_t pool_split_width(uint32_t max_count) {
+    uint32_t m = 1u;
+    while (m < max_count) m <<= 1;
+    return m;
+}
+// Does a round of m >= 1 items run one primitive per lane (M lanes per item)?  Wave-uniform, as everything about a round's shape.
+LJ_HD bool pool_round_splits(uint32_t m, uint32_t M) { return M > 1u && m * M <= 64u; }
+// log2 of W, the lanes per item of a round of m >= 1 items: the widest power of two W <= M with m * W <= 64 (0: one lane per item — every
+// round of more than 32 items, so every round but a pass's last).  pool_round_splits(m, M) exactly when this comes to log2 M > 0.
+LJ_HD uint32_t pool_round_shift(uint32_t m, uint32_t M) {
+    uint32_t shift = 0u;
+    while ((2u << shift) <= M && m * (2u << shift) <= 64u) shift++;
+    return shift;
+}
+// The lane's item of the round that starts at item r (to be held against n_items by the caller) ...
+LJ_HD uint32_t pool_round_item(uint32_t r, uint32_t lane, uint32_t shift) { return r + (lane >> shift); }
+// ... and the first primitive of that item's leaf it tests; the next ones follow in steps of W = 1 << shift, below the leaf's `count`
+LJ_HD uint32_t pool_round_prim(uint32_t lane, uint32_t shift) { return lane & ((1u << shift) - 1u); }
+
 } // namespace ljd

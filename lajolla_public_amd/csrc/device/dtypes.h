@@ -172,8 +172,9 @@ struct DScene {
     int32_t has_heterogeneous_medium;   // some medium is a grid volume (picks the k_volpath instantiation)
     int32_t vol_path_version;           // RenderOptions::vol_path_version (render.cpp:111-123): 1 and 2 are estimators of their own
     // tiny scenes only (mega.hip): the flat leaf table; n_scan_leaves (0 when the scene has none) is a multiple of 4, the first n_scan_used
-    // entries are leaves, the rest padding that is never entered
-    const DScanLeaf *scan_leaves; int32_t n_scan_leaves, n_scan_used;
+    // entries are leaves, the rest padding that is never entered; scan_split_m: the largest `count` among them rounded up to a power of
+    // two (dmegapool.h: pool_split_width; a refit moves boxes, never counts)
+    const DScanLeaf *scan_leaves; int32_t n_scan_leaves, n_scan_used, scan_split_m;
 };
 
 // ---- wavefront path queue: one slot per in-flight path, stored as eight arrays of 16-byte records so that every

@@ -50,6 +50,10 @@ struct ScanCtx {
     LJ_LDS unsigned long long *keys;    // closest hit of lane's extension ray: float bits of t << 32 | gprim << 16 | leaf-order index
     LJ_LDS uint8_t *occl;               // != 0: lane's shadow ray is blocked
     LJ_LDS uint16_t *items; uint32_t item_cap;
+    uint32_t split_m;                   // the largest leaf `count`, rounded up to a power of two (DScene::scan_split_m): lanes per item of a split round
+#if LJ_MEGA_ROUND_STATS
+    unsigned long long *round_stats;    // developer build (dconfig.h): kMegaRoundStats tallies; null in the ray queries
+#endif
     LJ_LDS uint64_t *st_rng;            // stash of camera samples (k_mega builds with STASH only): slot i holds sample st_base + i — its pcg32 state after the jitter draws
     LJ_LDS float *st_dir;               // and its primary direction at [i], [64 + i], [128 + i]
 };
@@ -121,9 +125,9 @@ __device__ __forceinline__ void scan_leaf_boxes2(const ScanCtx &sx, f3 org, f3 d
 
 // Closest hit of every lane's extension ray (has_e) and occlusion of its shadow ray (has_s), wave-synchronous: all 64 lanes
 // call it together.  Results: gprim (-1: miss), t, u, v exactly as k_extend reports them; occluded.
-// LANE_MAJOR: how the candidates are listed (mega_pool_lane_major below) — the order cannot change a result: the closest hit is a minimum
-// over a total order and occlusion an OR.
-template <bool SPHERES, bool LANE_MAJOR>
+// LANE_MAJOR: how the candidates are listed (mega_pool_lane_major below); SPLIT: a short last test round of a pass runs one primitive per
+// lane (mega_round_split below) — neither order can change a result: the closest hit is a minimum over a total order and occlusion an OR.
+template <bool SPHERES, bool LANE_MAJOR, bool SPLIT>
 __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool has_s, f3 org, f3 dir_e, float tnear_e, f3 dir_s, float tnear_s, float tfar_s,
                                            float &ht, float &hu, float &hv, int &gprim_out, bool &occluded) {
     // No floating-point contraction in here: u = U * (1 / S) must reach the shading code as the rounded product k_extend stores in
@@ -171,9 +175,19 @@ __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool h
             if (n_items == 0u) break;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-        // ---- test them, 64 at a time, whichever lane is free (lane-major: consecutive items mostly share a ray, its reads are LDS broadcasts)
+#if LJ_MEGA_ROUND_STATS
+        if (lane == 0u && sx.round_stats) {
+            atomicAdd(&sx.round_stats[0], 1ull); atomicAdd(&sx.round_stats[1], (unsigned long long)n_items); atomicAdd(&sx.round_stats[2], (unsigned long long)((n_items + 63u) / 64u));
+            atomicAdd(&sx.round_stats[3u + ((n_items - 1u) & 63u) / 8u], 1ull);
+        }
+#endif
+        // ---- test them, 64 at a time, whichever lane is free (lane-major: consecutive items mostly share a ray, its reads are LDS broadcasts).
+        // A lane walks the primitives of its item's leaf — except in a short last round (SPLIT; shift != 0, wave-uniform), where W = 1 << shift
+        // lanes share an item and each tests every W-th primitive of its leaf (dmegapool.h): on cbox (two triangles in all leaves but one, ~150
+        // items in a pass) the third round holds about 22 items and costs one triangle test instead of two
         for (uint32_t r = 0; r < n_items; r += 64u) {
-            const uint32_t slot = r + lane;
+            const uint32_t shift = SPLIT ? pool_round_shift(n_items - r, sx.split_m) : 0u;   // (more than 64 items left: not the last round, never split)
+            const uint32_t slot = pool_round_item(r, lane, shift);
             if (slot < n_items) {
                 const uint32_t it = sx.items[slot];
                 const uint32_t src = pool_item_lane(it), leaf = pool_item_leaf(it, (uint32_t)sx.n_used), kind = 1u - pool_item_ext(it);
@@ -181,8 +195,8 @@ __device__ __forceinline__ void scan_trace(const ScanCtx &sx, bool has_e, bool h
                 RayF ray;
                 ray.ox = o4.x; ray.oy = o4.y; ray.oz = o4.z; ray.dx = d4.x; ray.dy = d4.y; ray.dz = d4.z;
                 ray.tnear = d4.w; ray.tfar = kind ? o4.w : INFINITY;
-                const int first = sx.leaf_tab[2 * leaf], cnt = sx.leaf_tab[2 * leaf + 1];
-                for (int p = 0; p < cnt; p++) {
+                const int first = sx.leaf_tab[2 * leaf], cnt = sx.leaf_tab[2 * leaf + 1], step = 1 << shift;
+                for (int p = (int)pool_round_prim(lane, shift); p < cnt; p += step) {
                     const int pi = first + p, S = sx.prim_stride;
                     const v4f p0 = sx.lprims[pi], p1 = sx.lprims[S + pi], p2 = sx.lprims[2 * S + pi];
                     const int gprim = __float_as_int(p0.w);
@@ -258,7 +272,7 @@ __device__ __forceinline__ void stash_start(const DScene &sc, const DPass &pass,
 
 // LDS image of the scan area at byte offset `at` (16-byte aligned): [leaf table][primitives, transposed][4 x wave scratch]
 template <uint32_t ITEM_CAP, bool STASH>
-__device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at, uint32_t item_cap) {
+__device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at, uint32_t item_cap, unsigned long long *round_stats = nullptr) {
     ScanCtx sx;
     char *base = (char *)lj_smem + at;
     LJ_LDS int *lt = (LJ_LDS int *)base;
@@ -275,6 +289,10 @@ __device__ __forceinline__ ScanCtx stage_scan(const DScene &sc, uint32_t at, uin
     const uint32_t after = 64 * 48 + 64 * 8 + (STASH ? kWaveStashBytes : 0u);   // (without a stash st_rng / st_dir are never used)
     sx.occl = (LJ_LDS uint8_t *)(wave + after); sx.items = (LJ_LDS uint16_t *)(wave + after + 64);
     sx.item_cap = item_cap < ITEM_CAP ? item_cap : ITEM_CAP;   // (the launchers pass 1 .. ITEM_CAP: the pool is ITEM_CAP items whatever arrives)
+    sx.split_m = (uint32_t)sc.scan_split_m;
+#if LJ_MEGA_ROUND_STATS
+    sx.round_stats = round_stats;
+#endif
     return sx;
 }
 size_t scan_smem(int n_scan_leaves, int n_prims, uint32_t item_cap = kItemCap, bool stash = false) { return (((size_t)n_scan_leaves * 8 + 15) & ~(size_t)15) + (size_t)n_prims * 48 + 4 * (size_t)wave_scan_bytes(item_cap, stash); }
@@ -310,6 +328,17 @@ template <class Ft> constexpr uint32_t mega_item_cap() { return (mega_stash<Ft>(
 // So: the triangle-only five-wave Lambert build, and the ray queries; every other build pools in rounds, as before.
 template <class Ft, bool SPHERES> constexpr bool mega_pool_lane_major() { return !SPHERES && MegaOccupancy<Ft>::waves >= 5; }
 
+// Which builds split a short last test round of a pass by primitive (scan_trace, dmegapool.h).  On cbox the last round of a pass holds at most 32
+// items in 54.9 % of the passes; split, a pass issues 58 vector instructions fewer and 42 scalar ones more, and a render is 1.0 % faster (11.059 ->
+// 10.945 ms).  veach_mi pools in rounds, which fills its rounds (15.5 % of its last rounds hold at most 32 items): split, it was 0.8 % SLOWER
+// (profiles/mega_round_ab.txt).  So: the builds that pool lane-major, and the ray queries; every other build keeps the loop it had.
+// LJ_MEGA_ROUND_SPLIT (developer A/B): 0 nowhere, 1 as said, 2 every build.
+#ifndef LJ_MEGA_ROUND_SPLIT
+#define LJ_MEGA_ROUND_SPLIT 1
+#endif
+template <class Ft, bool SPHERES> constexpr bool mega_round_split() { return LJ_MEGA_ROUND_SPLIT >= 2 || (LJ_MEGA_ROUND_SPLIT == 1 && mega_pool_lane_major<Ft, SPHERES>()); }
+constexpr bool kQueryRoundSplit = LJ_MEGA_ROUND_SPLIT >= 1;
+
 // stats: [0] bounce iterations, [1] closest-hit rays, [2] shadow rays, [3] samples finished, [4] path steps (shade_path calls)
 // (VIEWS: the pass is a batch of cameras, dshade.h; same occupancy, same LDS — the stash has no per-view entry)
 template <class Ft, bool SPHERES, bool VIEWS>
@@ -317,7 +346,7 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
                                                               uint32_t item_cap, uint32_t *sample_counter, unsigned long long *stats) {
     stage_shade_tables<2>(sc, stg, 0u);
     constexpr bool STASH = mega_stash<Ft>();
-    const ScanCtx sx = stage_scan<mega_item_cap<Ft>(), STASH>(sc, scan_at, item_cap);
+    const ScanCtx sx = stage_scan<mega_item_cap<Ft>(), STASH>(sc, scan_at, item_cap, stats + 5);   // (the tallies of an LJ_MEGA_ROUND_STATS build)
     __syncthreads();
     const uint32_t lane = lane_id();
     ShadeCounters cnt; cnt.bounces = cnt.closest = cnt.shadow = cnt.done = 0;
@@ -396,7 +425,7 @@ __global__ void __launch_bounds__(kBlock, MegaOccupancy<Ft>::waves) k_mega(DScen
         opaque_state(ps);
         const bool has_e = live && !(ps.flags & PF_NO_EXT), has_s = live && ps.stfar > 0.0f;
         float ht, hu, hv; int gprim; bool occluded;
-        scan_trace<SPHERES, mega_pool_lane_major<Ft, SPHERES>()>(sx, has_e, has_s, ps.org, ps.dir, (ps.flags & 0xffffu) == 2u ? 0.0f : sc.eps, ps.sdir, sc.eps, ps.stfar, ht, hu, hv, gprim, occluded);
+        scan_trace<SPHERES, mega_pool_lane_major<Ft, SPHERES>(), mega_round_split<Ft, SPHERES>()>(sx, has_e, has_s, ps.org, ps.dir, (ps.flags & 0xffffu) == 2u ? 0.0f : sc.eps, ps.sdir, sc.eps, ps.stfar, ht, hu, hv, gprim, occluded);
         if (live) {
             if (has_s && !occluded) ps.rad = add_rounded(ps.rad, ps.nee);   // path_tracing.h:207 (k_shade adds it at the top of the next step)
             ps.ht = ht; ps.hu = hu; ps.hv = hv; ps.hcode = gprim + 1;
@@ -428,11 +457,11 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays_scan(DScene sc, const Ray
         if (act) { org = ld3(rays[i].org); dir = ld3(rays[i].dir); tn = rays[i].tnear; tf = rays[i].tfar; }
         float ht, hu, hv; int gprim; bool occluded;
         if (occ) {   // any hit in (tnear, tfar]: the shadow-ray slot
-            scan_trace<true, true>(sx, false, act, org, dir, 0.0f, dir, tn, tf, ht, hu, hv, gprim, occluded);
+            scan_trace<true, true, kQueryRoundSplit>(sx, false, act, org, dir, 0.0f, dir, tn, tf, ht, hu, hv, gprim, occluded);
             if (act) occ[i] = occluded ? 1 : 0;
         } else {
             // closest hit in (tnear, tfar]: the extension-ray slot has tfar = inf, so the far end is applied to the result
-            scan_trace<true, true>(sx, act, false, org, dir, tn, dir, 0.0f, 0.0f, ht, hu, hv, gprim, occluded);
+            scan_trace<true, true, kQueryRoundSplit>(sx, act, false, org, dir, tn, dir, 0.0f, 0.0f, ht, hu, hv, gprim, occluded);
             if (act) {
                 HitIO o; o.t = 0; o.u = 0; o.v = 0; o.shape_id = -1; o.prim_id = -1;
                 if (gprim >= 0 && ht <= tf) { const DPrimShade &ps = sc.prims[gprim]; o.t = ht; o.u = hu; o.v = hv; o.shape_id = ps.shape_id; o.prim_id = ps.prim_id; }

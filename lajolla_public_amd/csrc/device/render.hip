@@ -190,7 +190,11 @@ void render_mega(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &plan, ui
     lj_context *ctx = sc->ctx;
     LjStats &st = sc->stats;
     ensure_sample_rgb(ctx, plan, pix_per_pass);
-    if (!ctx->mega_state.p) ctx->mega_state.alloc(64);
+    // the launch's counter and statistics (an LJ_MEGA_ROUND_STATS build: and its tallies of the test rounds, dconfig.h)
+    constexpr size_t state_bytes = LJ_MEGA_ROUND_STATS ? 256 : 64;
+    static_assert(8 + (5 + ljd::kMegaRoundStats) * sizeof(unsigned long long) <= 256, "the tallies follow the five statistics");
+    unsigned long long rounds[ljd::kMegaRoundStats] = {};
+    if (!ctx->mega_state.p) ctx->mega_state.alloc(state_bytes);
     upload_pixel_list(ctx, plan, stream);
     HIP_CHECK(hipEventRecord(ctx->ev_begin, stream));
     const int per_cu = std::max(1, env_int("LJ_TUNE_MEGA_BLOCKS_PER_CU", ljd::mega_blocks_per_cu(sc->dscene, sc->scfg)));
@@ -205,7 +209,7 @@ void render_mega(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &plan, ui
     unsigned long long hstats[5] = {};
     for (uint64_t p0 = 0; p0 < plan.pixels->size(); p0 += pix_per_pass) {
         const Pass P = pass_at(sc, plan, p0, pix_per_pass);
-        HIP_CHECK(hipMemsetAsync(ctx->mega_state.p, 0, 64, stream));
+        HIP_CHECK(hipMemsetAsync(ctx->mega_state.p, 0, state_bytes, stream));
         uint32_t grab = grab_max;
         if (!grab_fixed) {
             const uint64_t waves = (uint64_t)ctx->n_cus * per_cu * 4, per_draw = P.total / (waves * draws);
@@ -229,8 +233,20 @@ void render_mega(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &plan, ui
             throw LjError(LJ_ERR_INTERNAL, "mega launch ended with " + std::to_string(h[3]) + " of " + std::to_string(P.total) + " samples finished");
         for (int k = 0; k < 5; k++) hstats[k] += h[k];
         st.samples += P.total;
+#if LJ_MEGA_ROUND_STATS
+        unsigned long long r[ljd::kMegaRoundStats];
+        HIP_CHECK(hipMemcpy(r, stats_dev + 5, sizeof(r), hipMemcpyDeviceToHost));
+        for (int k = 0; k < ljd::kMegaRoundStats; k++) rounds[k] += r[k];
+#endif
     }
     st.render_ms = close_timer(ctx, stream);
+    if (LJ_MEGA_ROUND_STATS && rounds[0]) {   // developer build only: the test rounds of the leaf scan, over the render
+        unsigned long long half = 0;
+        for (int k = 0; k < 4; k++) half += rounds[3 + k];
+        fprintf(stderr, "[mega round stats] passes %llu  items per pass %.1f  test rounds per pass %.3f  last round at most half full (<= 32 items) %.1f %% of passes\n",
+                rounds[0], (double)rounds[1] / (double)rounds[0], (double)rounds[2] / (double)rounds[0], 100.0 * (double)half / (double)rounds[0]);
+        for (int k = 0; k < 8; k++) fprintf(stderr, "[mega round stats] last round of %2d .. %2d items: %12llu passes  %5.1f %%\n", 8 * k + 1, 8 * k + 8, rounds[3 + k], 100.0 * (double)rounds[3 + k] / (double)rounds[0]);
+    }
     st.bounce_iterations = hstats[0]; st.rays_closest = hstats[1]; st.rays_shadow = hstats[2]; st.path_steps = hstats[4];
     // algorithmic HBM bytes of a mega launch: the finished radiance of every sample (12 B) and its pixel's list entry — the path state
     // never leaves the registers

@@ -3,6 +3,7 @@
 #include "flatten.h"
 #include "../device/dscan.h"
 #include "../device/drefit.h"
+#include "../device/dmegapool.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -107,6 +108,9 @@ ljd::DScene FlatScene::host_view() const {
     s.has_heterogeneous_medium = 0;
     for (const auto &m : media) if (m.kind == LJ_MEDIUM_HETEROGENEOUS) s.has_heterogeneous_medium = 1;
     s.scan_leaves = scan_leaves.empty() ? nullptr : scan_leaves.data(); s.n_scan_leaves = (int32_t)scan_leaves.size(); s.n_scan_used = scan_leaves.empty() ? 0 : n_scan_used;
+    uint32_t max_count = 0;   // (the padding records hold none)
+    for (const auto &L : scan_leaves) max_count = std::max(max_count, (uint32_t)L.count);
+    s.scan_split_m = (int32_t)ljd::pool_split_width(max_count);
     return s;
 }
 
