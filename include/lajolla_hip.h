@@ -285,6 +285,50 @@ int lj_render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, 
 int lj_render_views_device(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views,
                            float *rgb_device, void *hip_stream);
 
+/* ---- guide buffers beside the image
+ * What lj_render / lj_render_views render for the same arguments, and from the same camera samples up to five more buffers: the first-hit
+ * albedo, shading normal, depth and coverage, and the variance of the image.  One upload, one BVH; anti-aliased like the image.
+ * LJ_RNG_SAMPLE and the path / volpath integrators only.
+ *
+ * Sample s of pixel p uses the camera sample of every path kernel: pcg32 stream (pixel * spp + s) — the pixel inside its view for a batch —
+ * of the call's seed, first draw jy, second draw jx, the ray from the camera's origin with tnear = 0.
+ *   First surface: the closest hit of that ray.  A hit on a shape without a material (a medium boundary) is passed through: the ray goes
+ *   on from the float hit position in the same direction with tnear = LjSceneInfo.shadow_epsilon and tfar = inf.  A sample traces at most 16
+ *   such segments; one whose 16th still ends on a boundary is a miss.  The vertex of the final hit is the one lj_vertex_queries computes for
+ *   its segment (ray_spread = the camera's), so after a crossing the texture footprint comes from the last segment only.
+ *   Per sample, on a hit: a = the material's slot-0 texture as a Spectrum at the vertex uv and footprint ((1,1,1) for disneyclearcoat, whose
+ *   slot 0 is a Real); n = the vertex's shading normal (world space, not flipped, not renormalised); d = |position - camera origin|; hit = 1.
+ *   On a miss all four are 0.
+ *   Per pixel: albedo = sum a / spp, normal = sum n / spp, alpha = sum hit / spp, depth = sum d / sum hit (0 without a hit), rgb as lj_render,
+ *   variance[c] = sum_s (x_sc - rgb[c])^2 / (spp (spp - 1)) over the per-sample radiance x (what lj_render_samples returns) — the squared
+ *   standard error of rgb, computed in two passes; 0 when spp == 1.
+ *   All sums are float sums in a fixed order that depends on spp alone: results are bit-identical from call to call, for any
+ *   crop, share, pass size, pool size, and between a view of a batch and the single-camera call.
+ *
+ * rgb is bit-identical to lj_render / lj_render_views of the same arguments, and lj_get_stats afterwards is what that call would have
+ * left, except that render_ms also covers the extra launches.  Pixels outside the rank's share or the crop window are 0 in every buffer,
+ * so the ranks' buffers add up to the full ones.  Nothing is launched for a buffer that is not asked for.
+ * LJ_ERR_UNSUPPORTED: rng_mode LJ_RNG_TILE; a scene with one of the five auxiliary integrators.  LJ_ERR_INVALID_ARG: a NULL LjFeatureBuffers
+ * or one with all six pointers NULL; n_views < 0; n_views > 0 without views, or views with n_views == 0; everything lj_render_views checks
+ * of the views.  A refused call writes nothing.  (Device groups have no features call: render on each lj_group_scene_member.) */
+typedef struct LjFeatureBuffers {      /* any pointer may be NULL: not wanted */
+    float *rgb;       /* [n][h][w][3] */
+    float *albedo;    /* [n][h][w][3] */
+    float *normal;    /* [n][h][w][3] */
+    float *depth;     /* [n][h][w]    */
+    float *alpha;     /* [n][h][w]    */
+    float *variance;  /* [n][h][w][3] */
+} LjFeatureBuffers;
+/* n_views == 0 and views == NULL: the scene's own camera (n = 1); else as lj_render_views.  Blocking; host pointers. */
+int lj_render_features(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, const LjFeatureBuffers *out_host);
+/* Same, into caller-owned DEVICE memory; ordering on `hip_stream` as lj_render_device. */
+int lj_render_features_device(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views,
+                              const LjFeatureBuffers *out_device, void *hip_stream);
+/* Of the last lj_render_features* call on the scene (zeros after any other render): device time of the guide-buffer and of the variance
+ * launches, camera samples the guide-buffer kernel traced (segments after a crossing are not counted) and its launches (one per pass). */
+typedef struct LjFeatureStats { double features_ms, variance_ms; uint64_t feature_rays, feature_launches; } LjFeatureStats;
+int lj_get_feature_stats(const lj_scene *scene, LjFeatureStats *out);
+
 /* Per-sample radiance for the crop window: out[((y-y0)*(x1-x0) + (x-x0))*spp + s][3] — one path_tracing()
  * value (path_tracing.h:7-325) per entry, for path-by-path parity tests. */
 int lj_render_samples(lj_scene *scene, const LjRenderArgs *args, float *radiance_host);

@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 from . import _abi
-from ._abi import LjRenderArgs, LjSceneDesc, LjStats, LjSceneInfo, LjRay, LjHit, LjCamera
+from ._abi import LjRenderArgs, LjSceneDesc, LjStats, LjSceneInfo, LjRay, LjHit, LjCamera, LjFeatureBuffers, LjFeatureStats
 from ._abi import LJ_RNG_SAMPLE, LJ_RNG_TILE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -281,6 +281,61 @@ def render_views_device(scene, cameras, device_ptr, stream=None, **kw):
     args = make_args(**kw)
     cams = _camera_array(cameras)
     _check(load_library().lj_render_views_device(scene._h, C.byref(args), len(cameras), cams, C.c_void_p(int(device_ptr)), C.c_void_p(int(stream or 0))))
+
+
+FEATURES = ("albedo", "normal", "depth", "alpha", "variance")
+
+
+def _feature_names(features):
+    names = [features] if isinstance(features, str) else list(features)
+    for f in names:
+        if f not in FEATURES:
+            raise ValueError(f"unknown feature {f!r}: expected some of {FEATURES}")
+    if len(set(names)) != len(names):
+        raise ValueError("a feature is named twice")
+    return names
+
+
+def render_features(scene, cameras=None, features=FEATURES, **kw):
+    """render() / render_views() and, from the same camera samples, the first-hit guide buffers and the variance of the image
+    (lj_render_features): a dict of float32 arrays — "rgb" always, and each of `features` ("albedo", "normal", "depth", "alpha", "variance").
+    (h, w, 3) arrays, (h, w) for depth and alpha; with a camera list (n, h, w, 3) and (n, h, w).  "rgb" is bit-identical to render()."""
+    names = _feature_names(features)
+    if cameras is not None and len(cameras) == 0:
+        raise ValueError("render_features: an empty camera list (pass cameras=None for the scene's own camera)")
+    args = make_args(**kw)
+    lead = (scene.info.height, scene.info.width) if cameras is None else (len(cameras), scene.info.height, scene.info.width)
+    out = {}
+    bufs = LjFeatureBuffers()
+    for name in ["rgb"] + names:
+        c = _abi.FEATURE_CHANNELS[name]
+        out[name] = np.empty(lead + ((c,) if c > 1 else ()), np.float32)
+        setattr(bufs, name, out[name].ctypes.data)
+    cams = _camera_array(cameras) if cameras is not None else None
+    _check(load_library().lj_render_features(scene._h, C.byref(args), 0 if cameras is None else len(cameras), cams, C.byref(bufs)))
+    return out
+
+
+def render_features_device(scene, buffers, cameras=None, stream=None, **kw):
+    """Same, into caller-owned device memory, ordered on a HIP stream as render_device: `buffers` maps "rgb" / "albedo" / "normal" / "depth" /
+    "alpha" / "variance" to device pointers (e.g. a torch tensor's data_ptr()) of n * h * w * channels floats; a name left out is not computed."""
+    bufs = LjFeatureBuffers()
+    for name, ptr in buffers.items():
+        if name not in _abi.FEATURE_CHANNELS:
+            raise ValueError(f"unknown buffer {name!r}: expected some of {tuple(_abi.FEATURE_CHANNELS)}")
+        setattr(bufs, name, int(ptr) if ptr else None)
+    if cameras is not None and len(cameras) == 0:
+        raise ValueError("render_features_device: an empty camera list (pass cameras=None for the scene's own camera)")
+    args = make_args(**kw)
+    cams = _camera_array(cameras) if cameras is not None else None
+    _check(load_library().lj_render_features_device(scene._h, C.byref(args), 0 if cameras is None else len(cameras), cams, C.byref(bufs), C.c_void_p(int(stream or 0))))
+
+
+def feature_stats(scene):
+    """LjFeatureStats of the scene's last render_features* call (zeros after any other render)."""
+    st = LjFeatureStats()
+    _check(load_library().lj_get_feature_stats(scene._h, C.byref(st)))
+    return st
 
 
 def render_samples(scene, crop, **kw):

@@ -127,6 +127,18 @@ class LjStats(C.Structure):
                 ("mega_ms", C.c_double), ("mega_launches", C.c_uint64), ("mega_bytes", C.c_uint64), ("path_steps", C.c_uint64)]
 
 
+class LjFeatureBuffers(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p), ("variance", C.c_void_p)]
+
+
+class LjFeatureStats(C.Structure):
+    _fields_ = [("features_ms", C.c_double), ("variance_ms", C.c_double), ("feature_rays", C.c_uint64), ("feature_launches", C.c_uint64)]
+
+
+# the buffers of lj_render_features beside "rgb", in LjFeatureBuffers order, with their channel counts (1: no channel axis)
+FEATURE_CHANNELS = {"rgb": 3, "albedo": 3, "normal": 3, "depth": 1, "alpha": 1, "variance": 3}
+
+
 class LjSceneInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32), ("max_depth", C.c_int32),
                 ("rr_depth", C.c_int32), ("integrator", C.c_int32),
@@ -228,6 +240,9 @@ SYMBOLS = [
     ("lj_scene_read_bvh", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lj_render_views", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p]),
     ("lj_render_views_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p, C.c_void_p]),
+    ("lj_render_features", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.POINTER(LjFeatureBuffers)]),
+    ("lj_render_features_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.POINTER(LjFeatureBuffers), C.c_void_p]),
+    ("lj_get_feature_stats", C.c_int, [C.c_void_p, C.POINTER(LjFeatureStats)]),
     ("lj_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_occluded", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_get_stats", C.c_int, [C.c_void_p, C.POINTER(LjStats)]),

@@ -26,7 +26,7 @@ ORACLE_LIB = os.path.join(ROOT, "oracle", "_build", "liblj_oracle_asan.so" if _S
 TWIN_LIB = os.path.join(ROOT, "tests", "twin", "_build", "libljtwin_asan.so" if _SAN else "libljtwin.so")
 
 HOST_SOURCES = ["host/api_host.cpp", "host/scene_xml.cpp", "host/mesh_io.cpp", "host/image_io.cpp", "host/jpeg_decode.cpp", "host/exr_decode.cpp", "host/png_decode.cpp", "host/tga_bmp_decode.cpp", "host/flatten.cpp", "host/bvh.cpp"]
-HIP_SOURCES = ["device/kernels.hip", "device/extend.hip", "device/extend8.hip", "device/volpath.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip"]
+HIP_SOURCES = ["device/kernels.hip", "device/extend.hip", "device/extend8.hip", "device/volpath.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip"]
 ARCH = "gfx950"
 
 
@@ -266,6 +266,24 @@ def build_twin_refit(verbose=True):
     return TWIN_REFIT_LIB
 
 
+TWIN_FEATURES_LIB = os.path.join(ROOT, "tests", "twin_features", "_build", "libljtwinfeatures_asan.so" if _SAN else "libljtwinfeatures.so")
+
+
+def build_twin_features(verbose=True):
+    """Host build of the guide-buffer path of the device headers (device/dfeature.h: lj_render_features) for the CPU-side tests; the flags of build_twin."""
+    src = os.path.join(ROOT, "tests", "twin_features", "twin_features.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_FEATURES_LIB), exist_ok=True)
+    deps = [src] + _headers() + [os.path.join(CSRC, s) for s in ("host/flatten.cpp", "host/bvh.cpp")]
+    if _stale(TWIN_FEATURES_LIB, deps):
+        if verbose:
+            print("[build] compiling the host twin of the guide-buffer path (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2", "-ffp-contract=off"] + _SAN_FLAGS + _host_fma_flag() + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+              "-o", TWIN_FEATURES_LIB, src, os.path.join(CSRC, "host/flatten.cpp"), os.path.join(CSRC, "host/bvh.cpp"), "-lpthread"])
+    return TWIN_FEATURES_LIB
+
+
 def build_reference_subset():
     """oracle/_ref from the reference's own sources — only where /root/reference exists (this container)."""
     script = os.path.join(ROOT, "oracle", "ref_build.sh")
@@ -286,4 +304,5 @@ if __name__ == "__main__":
         build_twin_scan()
         build_twin_views()
         build_twin_refit()
+        build_twin_features()
     print(LIB)

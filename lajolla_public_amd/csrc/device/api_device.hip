@@ -69,6 +69,7 @@ int lj_context_create(int device_id, lj_context **out) {
         HIP_CHECK(hipHostMalloc((void **)&ctx->stats_host, 64, hipHostMallocDefault));
         HIP_CHECK(hipEventCreate(&ctx->ev_begin)); HIP_CHECK(hipEventCreate(&ctx->ev_end));
         HIP_CHECK(hipEventCreate(&ctx->ev_k0)); HIP_CHECK(hipEventCreate(&ctx->ev_k1));
+        HIP_CHECK(hipEventCreate(&ctx->ev_f0)); HIP_CHECK(hipEventCreate(&ctx->ev_f1)); HIP_CHECK(hipEventCreate(&ctx->ev_f2));
         *out = ctx.release();
     });
 }
@@ -84,7 +85,7 @@ void lj_context_destroy(lj_context *ctx) {
     if (ctx->ev_caller) (void)hipEventDestroy(ctx->ev_caller);
     if (ctx->blocks_host) (void)hipHostFree(ctx->blocks_host);
     if (ctx->stats_host) (void)hipHostFree(ctx->stats_host);
-    for (hipEvent_t e : {ctx->ev_begin, ctx->ev_end, ctx->ev_k0, ctx->ev_k1}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->ev_begin, ctx->ev_end, ctx->ev_k0, ctx->ev_k1, ctx->ev_f0, ctx->ev_f1, ctx->ev_f2}) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }
 
@@ -257,9 +258,8 @@ int lj_scene_read_bvh(const lj_scene *scene, int32_t which, void *out_host, int6
     });
 }
 
-static void render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_host, float *rgb_device, hipStream_t caller, const char *who) {
-    if (!scene || !views || (!rgb_host && !rgb_device)) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    if (n_views <= 0) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": n_views must be positive");
+// the camera table of a batch, every view checked against the scene's camera
+static std::vector<ljd::DCamera> view_table(const lj_scene *scene, int32_t n_views, const LjCamera *views, const char *who) {
     const lj::FlatScene &F = scene->flat;
     const uint64_t view_pixels = (uint64_t)F.cam.width * (uint64_t)F.cam.height;
     if ((uint64_t)n_views * view_pixels > (1ull << 31)) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": more than 2^31 pixels in the batch");
@@ -271,7 +271,61 @@ static void render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_vi
             views[v].medium_id != F.cam_medium)
             throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": view " + std::to_string(v) + " differs from the scene camera in film size, filter or medium");
     }
+    return table;
+}
+
+static void render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_host, float *rgb_device, hipStream_t caller, const char *who) {
+    if (!scene || !views || (!rgb_host && !rgb_device)) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    if (n_views <= 0) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": n_views must be positive");
+    const std::vector<ljd::DCamera> table = view_table(scene, n_views, views, who);
     render_frame(scene, make_views_plan(scene, args, n_views), &table, rgb_host, rgb_device, caller, timing_requested(args));
+}
+
+// lj_render_features / _device: every check first, then render_frame's steps with up to five more frames beside the image.
+// `out`: host pointers (on_device false: the frames live in the context's workspace and only those asked for are copied back) or device pointers.
+static void render_features(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, const LjFeatureBuffers *out, bool on_device, hipStream_t caller, const char *who) {
+    if (!scene || !out) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    float *const dst[6] = {out->rgb, out->albedo, out->normal, out->depth, out->alpha, out->variance};
+    if (std::none_of(dst, dst + 6, [](float *p) { return p != nullptr; })) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": no buffer asked for");
+    if (n_views < 0) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": n_views must not be negative");
+    if ((n_views > 0) != (views != nullptr)) throw LjError(LJ_ERR_INVALID_ARG, std::string(who) + ": n_views and views must both be given or both be left out");
+    if (scene->flat.integrator < LJ_INTEGRATOR_PATH) throw LjError(LJ_ERR_UNSUPPORTED, std::string(who) + ": the auxiliary integrators have no guide buffers (path and volpath only)");
+    if (args && args->rng_mode == LJ_RNG_TILE) throw LjError(LJ_ERR_UNSUPPORTED, std::string(who) + ": rng_mode must be LJ_RNG_SAMPLE (the per-tile schedule keeps no per-sample values)");
+    std::vector<ljd::DCamera> table;
+    if (n_views > 0) table = view_table(scene, n_views, views, who);
+    RenderPlan plan = n_views > 0 ? make_views_plan(scene, args, n_views) : make_plan(scene, args);
+    // ---- nothing was written up to here
+    lj_context *ctx = scene->ctx;
+    set_device(ctx);
+    hipStream_t s = ctx->stream;
+    if (caller) { HIP_CHECK(hipEventRecord(ctx->ev_caller, caller)); HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_caller, 0)); }
+    if (n_views > 0) {
+        const size_t table_bytes = table.size() * sizeof(ljd::DCamera);
+        ensure(ctx->view_table, table_bytes);
+        HIP_CHECK(hipMemcpyAsync(ctx->view_table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
+        plan.views_dev = (const ljd::DCamera *)ctx->view_table.p;
+    }
+    const size_t n_pix = (size_t)std::max(n_views, 1) * scene->flat.cam.width * scene->flat.cam.height;
+    const size_t chan[6] = {3, 3, 3, 1, 1, 3};
+    float *frame[6] = {};
+    if (on_device) for (int k = 0; k < 6; k++) frame[k] = dst[k];
+    else {
+        if (dst[0]) { ensure(ctx->frame, n_pix * 3 * sizeof(float)); frame[0] = (float *)ctx->frame.p; }
+        size_t need = 0;
+        for (int k = 1; k < 6; k++) if (dst[k]) need += n_pix * chan[k];
+        ensure(ctx->feature_frames, need * sizeof(float));
+        float *at = (float *)ctx->feature_frames.p;
+        for (int k = 1; k < 6; k++) if (dst[k]) { frame[k] = at; at += n_pix * chan[k]; }
+    }
+    for (int k = 0; k < 6; k++) if (frame[k]) HIP_CHECK(hipMemsetAsync(frame[k], 0, n_pix * chan[k] * sizeof(float), s));
+    plan.feat.albedo = frame[1]; plan.feat.normal = frame[2]; plan.feat.depth = frame[3]; plan.feat.alpha = frame[4]; plan.feat.variance = frame[5];
+    plan.feat.want = (frame[1] ? ljd::FEAT_ALBEDO : 0u) | (frame[2] ? ljd::FEAT_NORMAL : 0u) | (frame[3] ? ljd::FEAT_DEPTH : 0u) | (frame[4] ? ljd::FEAT_ALPHA : 0u) | (frame[5] ? ljd::FEAT_VARIANCE : 0u);
+    run_render(scene, plan, frame[0], nullptr, s, timing_requested(args));
+    if (!on_device) {
+        for (int k = 0; k < 6; k++) if (dst[k]) HIP_CHECK(hipMemcpyAsync(dst[k], frame[k], n_pix * chan[k] * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (caller) { HIP_CHECK(hipEventRecord(ctx->ev_caller, s)); HIP_CHECK(hipStreamWaitEvent(caller, ctx->ev_caller, 0)); }
 }
 
 int lj_render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_host) {
@@ -280,6 +334,20 @@ int lj_render_views(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, 
 
 int lj_render_views_device(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, float *rgb_device, void *hip_stream) {
     return lj::guard([&]() { render_views(scene, args, n_views, views, nullptr, rgb_device, (hipStream_t)hip_stream, "lj_render_views_device"); });
+}
+
+int lj_render_features(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, const LjFeatureBuffers *out_host) {
+    return lj::guard([&]() { render_features(scene, args, n_views, views, out_host, false, nullptr, "lj_render_features"); });
+}
+
+int lj_render_features_device(lj_scene *scene, const LjRenderArgs *args, int32_t n_views, const LjCamera *views, const LjFeatureBuffers *out_device, void *hip_stream) {
+    return lj::guard([&]() { render_features(scene, args, n_views, views, out_device, true, (hipStream_t)hip_stream, "lj_render_features_device"); });
+}
+
+int lj_get_feature_stats(const lj_scene *scene, LjFeatureStats *out) {
+    if (!scene || !out) { lj::set_last_error("lj_get_feature_stats: null argument"); return LJ_ERR_INVALID_ARG; }
+    *out = scene->feature_stats;
+    return LJ_OK;
 }
 
 int lj_render_samples(lj_scene *scene, const LjRenderArgs *args, float *radiance_host) {

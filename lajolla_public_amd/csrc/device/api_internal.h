@@ -32,6 +32,10 @@ void launch_aux(const DScene &sc, const DPass &pass, uint32_t n_pixels, int inte
 void launch_volpath(const DScene &sc, const DPass &pass, uint32_t n_samples, uint32_t *counters, const ExtendConfig &cfg, int shade_variant, bool plain, int *spill, int grid, hipStream_t s);
 int volpath_blocks_per_cu(const DScene &sc);
 void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
+// features.hip: the guide buffers and the variance of a pass (lj_render_features; `want`: the FEAT_* bits of dtypes.h)
+int features_grid(uint64_t n_pixels, uint32_t spp, int n_cus);
+void launch_features(const DScene &sc, const DPass &pass, uint32_t n_pixels, uint32_t want, float *albedo, float *normal, float *depth, float *alpha, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
+void launch_resolve_variance(const DPass &pass, uint32_t n_pixels, float *variance, hipStream_t s);
 // mega.hip
 size_t mega_smem(const DScene &sc, const ShadeConfig &scfg);
 int mega_blocks_per_cu(const DScene &sc, const ShadeConfig &scfg);
@@ -110,6 +114,9 @@ struct lj_context {
     ljd::DBlockState *blocks_host = nullptr;  // pinned, kMaxBlocks entries
     unsigned long long *stats_host = nullptr; // pinned, 8 entries: where a launch's statistics are read back (one wait per pass, no staged copy)
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
+    // lj_render_features: the host variant's five buffers, and the events around a pass's variance and feature launches (recorded in a features call only)
+    DevBuf feature_frames;
+    hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr, ev_f2 = nullptr;
 };
 
 struct lj_scene {
@@ -126,6 +133,7 @@ struct lj_scene {
     std::shared_ptr<const std::vector<uint32_t>> views_pixels; uint64_t views_pixels_key = 0;   // ... and the last batch plan's (make_views_plan)
     std::vector<int64_t> shape_first_gprim;   // global primitive id of each shape's first primitive (shape order, then triangle order)
     LjStats stats{};
+    LjFeatureStats feature_stats{};   // of the last lj_render_features* call; zeros after any other render
 };
 
 inline void set_device(lj_context *ctx) { HIP_CHECK(hipSetDevice(ctx->device)); }
@@ -149,6 +157,9 @@ struct RenderPlan {
     // a batch of cameras (lj_render_views): `pixels` lists e = v*w*h + y*w + x — the single-view list, in its order, once per view — and
     // views_dev is the batch's camera table on the device (0 / null: the scene's one camera)
     int n_views = 0; const ljd::DCamera *views_dev = nullptr;
+    // a features request (lj_render_features): device frames of the plan's size, written at the plan's pixels after every pass's resolve;
+    // want: the FEAT_* bits (dtypes.h) of the frames that are asked for, 0: none — the render is then exactly lj_render's
+    struct Features { uint32_t want = 0; float *albedo = nullptr, *normal = nullptr, *depth = nullptr, *alpha = nullptr, *variance = nullptr; } feat;
 };
 inline bool timing_requested(const LjRenderArgs *a) { return a && (a->flags & 1u); }   // (LjRenderArgs::flags bit 0: time every kernel)
 RenderPlan make_plan(lj_scene *sc, const LjRenderArgs *a);

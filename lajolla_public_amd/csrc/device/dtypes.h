@@ -239,6 +239,9 @@ struct DPass {
 inline void set_pass_divisors(DPass &p, uint32_t spp, uint32_t width) { p.spp = spp; p.by_spp = make_fast_div(spp); p.by_width = make_fast_div(width); }
 inline void set_pass_views(DPass &p, const DCamera *views, uint32_t width, uint32_t height) { p.views = views; p.by_height = make_fast_div(height); p.view_pixels = width * height; }
 
+// what a features request asks of a pass (lj_render_features: RenderPlan::feat on the host, the `want` of k_features)
+enum : uint32_t { FEAT_ALBEDO = 1u, FEAT_NORMAL = 2u, FEAT_DEPTH = 4u, FEAT_ALPHA = 8u, FEAT_VARIANCE = 16u, FEAT_FIRST_HIT = 15u };
+
 // the per-tile schedule (LJ_RNG_TILE, dtile.h): one launch's (or one host walk's) view of the job
 struct DTileJob {
     const uint32_t *tiles;        // tile ids t = ty * ntx + tx, t % world_size == rank, touching the crop window

@@ -10,7 +10,9 @@
 //   - LjStats: every field is filled by the same rule in every driver, the fields a driver leaves zero included, and wavefront_steps
 //     counts lane 0 only in the wavefront driver;
 //   - error texts and codes;
-//   - the workspace grows exactly when it has to: a render that fits the buffers the context holds allocates nothing.
+//   - the workspace grows exactly when it has to: a render that fits the buffers the context holds allocates nothing;
+//   - a render without a features request (RenderPlan::feat.want == 0: every entry point but lj_render_features*) enqueues nothing of
+//     finish_pass's features hook, records none of its events and touches no buffer for it.
 #include "api_internal.h"
 
 namespace {
@@ -68,8 +70,31 @@ void ensure_sample_rgb(lj_context *ctx, const RenderPlan &plan, uint64_t pix_per
 
 // The end of a pass on the render stream: its samples resolved into the frame and copied to the host at the pass's place in the list.
 // stats_dev (k_mega): five 64-bit statistics, read into ctx->stats_host by the same wait.  Without either host copy nothing waits.
-void finish_pass(lj_context *ctx, const RenderPlan &plan, const Pass &P, float *rgb_dev, float *samples_host, const void *stats_dev, hipStream_t stream) {
+// A features request (plan.feat.want, lj_render_features) adds, after the resolve and while sample_rgb still holds the pass: the variance
+// of the pass's samples and the guide buffers of its pixels, between events of their own; then it waits for them, so that the events can
+// serve the next pass.  Without a request nothing here is enqueued that was not before.
+void finish_pass(lj_scene *sc, const RenderPlan &plan, const Pass &P, float *rgb_dev, float *samples_host, const void *stats_dev, hipStream_t stream) {
+    lj_context *ctx = sc->ctx;
     if (rgb_dev) ljd::launch_resolve(P.d, (uint32_t)P.np, rgb_dev, stream);
+    if (plan.feat.want) {
+        const RenderPlan::Features &f = plan.feat;
+        LjFeatureStats &fs = sc->feature_stats;
+        HIP_CHECK(hipEventRecord(ctx->ev_f0, stream));
+        if (f.want & ljd::FEAT_VARIANCE) ljd::launch_resolve_variance(P.d, (uint32_t)P.np, f.variance, stream);
+        HIP_CHECK(hipEventRecord(ctx->ev_f1, stream));
+        if (f.want & ljd::FEAT_FIRST_HIT) {
+            const int grid = ljd::features_grid(P.np, (uint32_t)plan.spp, ctx->n_cus);
+            // (run_render made room for the largest pass before the driver carved its own stacks from the buffer: it must not move now)
+            if (sc->ecfg.spill_levels > 0 && ctx->spill.bytes < (size_t)sc->ecfg.spill_levels * (size_t)grid * 256 * sizeof(int))
+                throw LjError(LJ_ERR_INTERNAL, "the overflow stacks do not hold a features launch");
+            ljd::launch_features(sc->dscene, P.d, (uint32_t)P.np, f.want, f.albedo, f.normal, f.depth, f.alpha, sc->ecfg, sc->ecfg.spill_levels > 0 ? (int *)ctx->spill.p : nullptr, grid, stream);
+            fs.feature_rays += P.total; fs.feature_launches++;
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ctx->ev_f2, stream));
+        HIP_CHECK(hipEventSynchronize(ctx->ev_f2));
+        fs.variance_ms += elapsed_ms(ctx->ev_f0, ctx->ev_f1); fs.features_ms += elapsed_ms(ctx->ev_f1, ctx->ev_f2);
+    }
     if (stats_dev) HIP_CHECK(hipMemcpyAsync(ctx->stats_host, stats_dev, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     if (samples_host) HIP_CHECK(hipMemcpyAsync(samples_host + P.p0 * (uint64_t)plan.spp * 3, ctx->sample_rgb.p, P.total * 12, hipMemcpyDeviceToHost, stream));
     if (stats_dev || samples_host) HIP_CHECK(hipStreamSynchronize(stream));
@@ -170,7 +195,7 @@ void render_volpath(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &plan,
                             ensure_spill(ctx, sc->ecfg.spill_levels, (uint32_t)grid), grid, stream);
         HIP_CHECK(hipGetLastError());
         st.samples += P.total; st.wavefront_steps++;
-        finish_pass(ctx, plan, P, rgb_dev, samples_host, nullptr, stream);
+        finish_pass(sc, plan, P, rgb_dev, samples_host, nullptr, stream);
     }
     st.render_ms = close_timer(ctx, stream);
     unsigned long long nb = 0;
@@ -227,7 +252,7 @@ void render_mega(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &plan, ui
             st.mega_ms += elapsed_ms(ctx->ev_k0, ctx->ev_k1);
         }
         st.mega_launches++; st.wavefront_steps++;
-        finish_pass(ctx, plan, P, rgb_dev, samples_host, stats_dev, stream);   // (always waits: the launch's statistics)
+        finish_pass(sc, plan, P, rgb_dev, samples_host, stats_dev, stream);   // (always waits: the launch's statistics)
         const unsigned long long *h = ctx->stats_host;
         if (h[3] != P.total)
             throw LjError(LJ_ERR_INTERNAL, "mega launch ended with " + std::to_string(h[3]) + " of " + std::to_string(P.total) + " samples finished");
@@ -465,7 +490,7 @@ void render_wavefront(lj_scene *sc, const ljd::DScene &ds, const RenderPlan &pla
         run_lanes(sc, ds, g, P, lanes, timing, xstats);
         account_pass(sc, g, P);
         // (both lanes were synchronised with the host above, so the caller's stream may read what the second lane wrote)
-        finish_pass(ctx, plan, P, rgb_dev, samples_host, nullptr, stream);
+        finish_pass(sc, plan, P, rgb_dev, samples_host, nullptr, stream);
     }
     sc->stats.render_ms = close_timer(ctx, stream);
     if (xstats) {
@@ -557,6 +582,7 @@ RenderPlan make_views_plan(lj_scene *sc, const LjRenderArgs *a, int n_views) {
 void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *samples_host, hipStream_t stream, bool timing) {
     set_device(sc->ctx);
     sc->stats = LjStats{};
+    sc->feature_stats = LjFeatureStats{};
     if (plan.pixels->empty()) return;
     if (sc->flat.integrator < LJ_INTEGRATOR_PATH) return render_aux(sc, plan, rgb_dev, samples_host, stream);
     ljd::DScene ds = sc->dscene;   // the scene as the plan's kernels see it
@@ -566,6 +592,8 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
     // (LJ_TUNE_PASS_SAMPLES, a developer knob: small passes, so that a test can put a pass boundary anywhere — inside a view of a batch, say — at a small size)
     const uint64_t max_samples_pass = (uint64_t)std::min(1 << 27, std::max(64, env_int("LJ_TUNE_PASS_SAMPLES", 1 << 27)));
     const uint64_t pix_per_pass = std::min<uint64_t>(std::max<uint64_t>(1, max_samples_pass / (uint64_t)plan.spp), plan.pixels->size());
+    // a features request: room in the overflow stacks for the guide-buffer launch of the largest pass, before a driver takes its part of them
+    if (plan.feat.want & ljd::FEAT_FIRST_HIT) ensure_spill(sc->ctx, sc->ecfg.spill_levels, (uint32_t)ljd::features_grid(pix_per_pass, (uint32_t)plan.spp, sc->ctx->n_cus));
     if (sc->flat.integrator == LJ_INTEGRATOR_VOLPATH) return render_volpath(sc, ds, plan, pix_per_pass, rgb_dev, samples_host, stream);
     if (ljd::mega_smem(sc->dscene, sc->scfg) > 0 && mega_enabled()) return render_mega(sc, ds, plan, pix_per_pass, rgb_dev, samples_host, stream, timing);
     render_wavefront(sc, ds, plan, pix_per_pass, rgb_dev, samples_host, stream, timing);
