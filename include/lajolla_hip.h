@@ -329,6 +329,36 @@ int lj_render_features_device(lj_scene *scene, const LjRenderArgs *args, int32_t
 typedef struct LjFeatureStats { double features_ms, variance_ms; uint64_t feature_rays, feature_launches; } LjFeatureStats;
 int lj_get_feature_stats(const lj_scene *scene, LjFeatureStats *out);
 
+/* ---- Denoising: an edge-stopping a-trous filter over the buffers of lj_render_features.  A pure image operation on a context: no
+ * scene, no BVH, no render plan.  The rule — taps, weights, order of the float sums — is spelled out in csrc/device/ddenoise.h (shared by
+ * the kernels and a host twin, which agree bit for bit) and in DESIGN.md 3.8.  In short: `iterations` passes with step 1, 2, 4, ..., each a
+ * 5 x 5 B3-spline stencil whose weights are multiplied by max(0, 1 - x)^2 stopping terms on the normal, relative depth, albedo and — scaled
+ * by the 3 x 3-prefiltered variance — the colour difference of centre and tap; the variance is filtered with the squared weights.
+ * in: n images of height x width, laid out as LjFeatureBuffers says.  rgb is required; variance, albedo, normal and depth are optional
+ * (NULL: that stopping term is left out); alpha is not read.  INPUTS MUST BE FINITE: the library does not scan them.
+ * LJ_DENOISE_DEMODULATE (needs albedo): the filter runs on rgb / (albedo + 1e-3) and multiplies the result back.
+ * rgb_out: [n][h][w][3], may be in->rgb (every input is read before anything is written); variance_out (may be NULL; needs in->variance):
+ * the filtered variance.  Results are bit-identical from call to call, for the host and the device variant and for any LJ_TUNE_* setting.
+ * LJ_ERR_INVALID_ARG: NULL ctx, in, in->rgb or rgb_out; n, width or height <= 0; n * width * height > 2^31; iterations > 8; a sigma that is
+ * negative or not finite; LJ_DENOISE_DEMODULATE without in->albedo; variance_out without in->variance.  A refused call writes nothing. */
+enum { LJ_DENOISE_DEMODULATE = 1 };
+typedef struct LjDenoiseArgs {         /* every field: <= 0 (flags: 0) for the default */
+    int32_t iterations;                /* default 5, at most 8 */
+    uint32_t flags;                    /* LJ_DENOISE_* */
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo;   /* defaults 4, 0.5, 0.1, 0.25 */
+} LjDenoiseArgs;
+/* Blocking; host pointers.  args NULL: the defaults. */
+int lj_denoise(lj_context *ctx, int32_t n, int32_t width, int32_t height, const LjFeatureBuffers *in_host,
+               const LjDenoiseArgs *args, float *rgb_out_host, float *variance_out_host);
+/* Same on caller-owned DEVICE memory of the context's device; ordering on `hip_stream` as lj_render_device — the buffers that
+ * lj_render_features_device filled on that stream can be passed straight on. */
+int lj_denoise_device(lj_context *ctx, int32_t n, int32_t width, int32_t height, const LjFeatureBuffers *in_device,
+                      const LjDenoiseArgs *args, float *rgb_out_device, float *variance_out_device, void *hip_stream);
+/* Of the last lj_denoise* call on the context (it waits for that call's launches): their device time, their number (iterations + 2:
+ * pack, one per iteration, unpack) and n * width * height.  A scene's LjStats is not touched by a denoise call. */
+typedef struct LjDenoiseStats { double denoise_ms; uint64_t launches, pixels; } LjDenoiseStats;
+int lj_get_denoise_stats(const lj_context *ctx, LjDenoiseStats *out);
+
 /* Per-sample radiance for the crop window: out[((y-y0)*(x1-x0) + (x-x0))*spp + s][3] — one path_tracing()
  * value (path_tracing.h:7-325) per entry, for path-by-path parity tests. */
 int lj_render_samples(lj_scene *scene, const LjRenderArgs *args, float *radiance_host);

@@ -140,6 +140,7 @@ class Context:
     def __init__(self, device=0):
         lib = load_library()
         self._h = C.c_void_p()
+        self.device = int(device)
         self._scenes = 0        # live Scene objects on this context
         self._released = False  # __del__ has run while scenes were still alive: the last scene destroys the context
         _check(lib.lj_context_create(int(device), C.byref(self._h)))
@@ -335,6 +336,118 @@ def feature_stats(scene):
     """LjFeatureStats of the scene's last render_features* call (zeros after any other render)."""
     st = LjFeatureStats()
     _check(load_library().lj_get_feature_stats(scene._h, C.byref(st)))
+    return st
+
+
+DENOISE_SIGMAS = ("sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo")
+_default_ctx = None
+
+
+def make_denoise_args(iterations=0, demodulate=False, **sigmas):
+    """LjDenoiseArgs: iterations (<= 0: the default 5, at most 8), demodulate, and sigma_color / sigma_normal / sigma_depth / sigma_albedo (0: the default)."""
+    for k in sigmas:
+        if k not in DENOISE_SIGMAS:
+            raise ValueError(f"unknown argument {k!r}: expected some of {DENOISE_SIGMAS}")
+    if int(iterations) > 8:
+        raise ValueError("denoise: at most 8 iterations")
+    a = _abi.LjDenoiseArgs()
+    a.iterations = max(int(iterations), 0)
+    a.flags = _abi.LJ_DENOISE_DEMODULATE if demodulate else 0
+    for k, v in sigmas.items():
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"denoise: {k} must be finite and not negative")
+        setattr(a, k, float(v))
+    return a
+
+
+def _denoise_buffers(buffers, demodulate):
+    for name in buffers:
+        if name not in _abi.FEATURE_CHANNELS:
+            raise ValueError(f"unknown buffer {name!r}: expected some of {tuple(_abi.FEATURE_CHANNELS)}")
+    if buffers.get("rgb") is None:
+        raise ValueError("denoise: the buffers must hold \"rgb\"")
+    if demodulate and buffers.get("albedo") is None:
+        raise ValueError("denoise: demodulate=True needs the \"albedo\" buffer (pass demodulate=False to filter rgb itself)")
+
+
+def denoise(buffers, ctx=None, iterations=0, demodulate=True, **sigmas):
+    """The edge-stopping a-trous filter of lj_denoise over the dict render_features returns — one image, (h, w, 3), or a batch, (n, h, w, 3) —
+    with whichever of "variance", "albedo", "normal" and "depth" it holds ("alpha" is not read): {"rgb": the filtered image, "variance": the
+    filtered variance or None without a variance buffer}.  demodulate: filter rgb / (albedo + 1e-3) and multiply back (needs "albedo").
+    sigma_color / sigma_normal / sigma_depth / sigma_albedo and iterations: 0 for the defaults (4, 0.5, 0.1, 0.25; 5).  Inputs must be finite.
+    ctx: the Context to run on (None: one on device 0, created at the first such call and kept)."""
+    global _default_ctx
+    _denoise_buffers(buffers, demodulate)
+    args = make_denoise_args(iterations, demodulate, **sigmas)
+    rgb = np.ascontiguousarray(buffers["rgb"], np.float32)
+    if rgb.ndim not in (3, 4) or rgb.shape[-1] != 3 or 0 in rgb.shape:
+        raise ValueError("denoise: \"rgb\" must be (h, w, 3) or (n, h, w, 3) and not empty")
+    lead = rgb.shape[:-1]
+    n, (h, w) = (1 if rgb.ndim == 3 else lead[0]), lead[-2:]
+    bufs, keep = LjFeatureBuffers(), [rgb]
+    bufs.rgb = rgb.ctypes.data
+    for name in ("variance", "albedo", "normal", "depth"):
+        if buffers.get(name) is None:
+            continue
+        a = np.ascontiguousarray(buffers[name], np.float32)
+        c = _abi.FEATURE_CHANNELS[name]
+        if a.shape != lead + ((c,) if c > 1 else ()):
+            raise ValueError(f"denoise: {name!r} has shape {a.shape}, which does not go with rgb's {rgb.shape}")
+        keep.append(a)
+        setattr(bufs, name, a.ctypes.data)
+    if ctx is None:
+        if _default_ctx is None:
+            _default_ctx = Context(0)
+        ctx = _default_ctx
+    out = {"rgb": np.empty(rgb.shape, np.float32), "variance": np.empty(rgb.shape, np.float32) if bufs.variance else None}
+    _check(load_library().lj_denoise(ctx._h, n, w, h, C.byref(bufs), C.byref(args), out["rgb"].ctypes.data_as(C.c_void_p),
+                                     out["variance"].ctypes.data_as(C.c_void_p) if bufs.variance else None))
+    return out
+
+
+def denoise_device(ctx, buffers, n, width, height, rgb_out, variance_out=None, stream=None, iterations=0, demodulate=True, **sigmas):
+    """Same on device memory of ctx's device, ordered on a HIP stream as render_device: `buffers` maps "rgb" and any of "variance", "albedo",
+    "normal", "depth" to device pointers of n * height * width * channels floats (what render_features_device filled); rgb_out (may be
+    buffers["rgb"]) and variance_out (optional; needs "variance") are device pointers of n * height * width * 3 floats.  Asynchronous."""
+    _denoise_buffers(buffers, demodulate)
+    if variance_out and not buffers.get("variance"):
+        raise ValueError("denoise_device: variance_out needs the \"variance\" buffer")
+    if not rgb_out:
+        raise ValueError("denoise_device: no rgb_out")
+    args = make_denoise_args(iterations, demodulate, **sigmas)
+    bufs = LjFeatureBuffers()
+    for name, ptr in buffers.items():
+        setattr(bufs, name, int(ptr) if ptr else None)
+    _check(load_library().lj_denoise_device(ctx._h, int(n), int(width), int(height), C.byref(bufs), C.byref(args), C.c_void_p(int(rgb_out)),
+                                            C.c_void_p(int(variance_out)) if variance_out else None, C.c_void_p(int(stream or 0))))
+
+
+def render_denoised(scene, cameras=None, iterations=0, demodulate=True, sigmas=None, **kw):
+    """render_features_device and denoise_device back to back on the scene's device, no host copy in between: {"rgb", "variance"} as
+    denoise() returns them, bit-identical to denoise(render_features(scene, cameras, **kw)).  Device memory comes from torch.
+    sigmas: a dict of sigma_* values; **kw: the render's arguments (spp, seed, ...)."""
+    import torch
+    if cameras is not None and len(cameras) == 0:
+        raise ValueError("render_denoised: an empty camera list (pass cameras=None for the scene's own camera)")
+    make_denoise_args(iterations, demodulate, **(sigmas or {}))
+    n = 1 if cameras is None else len(cameras)
+    h, w = scene.info.height, scene.info.width
+    with torch.cuda.device(scene._ctx.device):
+        stream = torch.cuda.current_stream()
+        names = ("rgb",) + FEATURES
+        t = {k: torch.empty((n, h, w) + ((3,) if _abi.FEATURE_CHANNELS[k] == 3 else ()), device="cuda", dtype=torch.float32) for k in names}
+        out_var = torch.empty((n, h, w, 3), device="cuda", dtype=torch.float32)
+        render_features_device(scene, {k: t[k].data_ptr() for k in names}, cameras=cameras, stream=stream.cuda_stream, **kw)
+        denoise_device(scene._ctx, {k: t[k].data_ptr() for k in names}, n, w, h, t["rgb"].data_ptr(), out_var.data_ptr(), stream=stream.cuda_stream,
+                       iterations=iterations, demodulate=demodulate, **(sigmas or {}))
+        rgb, var = t["rgb"].cpu().numpy(), out_var.cpu().numpy()
+    return {"rgb": rgb if cameras is not None else rgb[0], "variance": var if cameras is not None else var[0]}
+
+
+def denoise_stats(ctx):
+    """LjDenoiseStats of the context's last denoise* call: device time of its launches (waits for them), their number, the pixel count."""
+    st = _abi.LjDenoiseStats()
+    _check(load_library().lj_get_denoise_stats(ctx._h, C.byref(st)))
     return st
 
 

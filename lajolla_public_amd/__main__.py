@@ -1,24 +1,26 @@
-"""`python -m lajolla_public_amd [-o output_file_name] [--spp N] [--rng tile|sample] [--features] [--gpus N | --devices 0,1,..] filename.xml ...` — the reference's
+"""`python -m lajolla_public_amd [-o output_file_name] [--spp N] [--rng tile|sample] [--features] [--denoise] [--gpus N | --devices 0,1,..] filename.xml ...` — the reference's
 driver loop (main.cpp:12-51) on the HIP path: parse, render, write to `-o` or the scene's own output file name (PFM / EXR).
 `-t num_threads` is accepted and ignored (the render does not run on host threads).  `--gpus N` renders on the first N devices of
 the node from this one process (a device group: tiles sharded t % N, one RCCL reduce); `--devices` names them (ids may repeat:
 logical ranks on one GPU).  `--rng tile` draws the random numbers in the reference's own order (one pcg32 stream per 16x16 tile,
 LJ_RNG_TILE: slower, for reproducing a reference render); the default `--rng sample` gives every pixel sample a stream of its own.
 `--features` also writes the guide buffers of lj_render_features beside the image, as <stem>.albedo.exr, .normal.exr, .depth.exr, .alpha.exr
-and .variance.exr (one-channel buffers replicated to RGB); one device, `--rng sample`, the path and volpath integrators."""
+and .variance.exr (one-channel buffers replicated to RGB); one device, `--rng sample`, the path and volpath integrators.
+`--denoise` also writes <stem>.denoised.exr: the image filtered by lj_denoise over those guide buffers (it renders them, under the conditions
+of `--features`, but writes the guide files only with `--features`)."""
 import os
 import sys
 import time
 
 from . import _abi
-from . import FEATURES, Context, DeviceGroup, GroupScene, Scene, parse_scene, render, render_features, render_group, write_image
+from . import FEATURES, Context, DeviceGroup, GroupScene, Scene, denoise, parse_scene, render, render_features, render_group, write_image
 
 
 def main(argv):
     if not argv:
-        print("[Usage] python -m lajolla_public_amd [-t num_threads] [-o output_file_name] [--spp N] [--rng tile|sample] [--features] [--gpus N | --devices i,j,..] filename.xml")
+        print("[Usage] python -m lajolla_public_amd [-t num_threads] [-o output_file_name] [--spp N] [--rng tile|sample] [--features] [--denoise] [--gpus N | --devices i,j,..] filename.xml")
         return 0
-    output, spp, filenames, devices, rng_mode, features = "", 0, [], None, _abi.LJ_RNG_SAMPLE, False
+    output, spp, filenames, devices, rng_mode, features, denoised = "", 0, [], None, _abi.LJ_RNG_SAMPLE, False, False
     i = 0
     while i < len(argv):
         if argv[i] == "-t":
@@ -38,6 +40,8 @@ def main(argv):
             rng_mode = modes[argv[i]]
         elif argv[i] == "--features":
             features = True
+        elif argv[i] == "--denoise":
+            denoised = True
         elif argv[i] == "--gpus":
             i += 1
             devices = list(range(int(argv[i])))
@@ -50,6 +54,9 @@ def main(argv):
     if features and ((devices and len(devices) > 1) or rng_mode != _abi.LJ_RNG_SAMPLE):
         print("--features: one device and --rng sample only (device groups and the per-tile schedule have no guide buffers)", file=sys.stderr)
         return 2
+    if denoised and ((devices and len(devices) > 1) or rng_mode != _abi.LJ_RNG_SAMPLE):
+        print("--denoise: one device and --rng sample only (the filter needs the guide buffers, which device groups and the per-tile schedule do not have)", file=sys.stderr)
+        return 2
     group = DeviceGroup(devices) if devices and len(devices) > 1 else None
     ctx = None if group else Context(devices[0] if devices else 0)
     for filename in filenames:
@@ -60,8 +67,8 @@ def main(argv):
         print(f"Done. Took {time.perf_counter() - t0:.6g} seconds.")
         print("Rendering...")
         t0 = time.perf_counter()
-        buffers = render_features(sc, spp=spp) if features else {}
-        img = buffers["rgb"] if features else (render_group(sc, spp=spp, rng_mode=rng_mode) if group else render(sc, spp=spp, rng_mode=rng_mode))
+        buffers = render_features(sc, spp=spp) if features or denoised else {}
+        img = buffers["rgb"] if buffers else (render_group(sc, spp=spp, rng_mode=rng_mode) if group else render(sc, spp=spp, rng_mode=rng_mode))
         if output == "":
             output = hs.desc.output_filename.decode()
         print(f"Done. Took {time.perf_counter() - t0:.6g} seconds.")
@@ -72,6 +79,10 @@ def main(argv):
             path = os.path.splitext(output)[0] + "." + name + ".exr"
             write_image(path, b if b.ndim == 3 else b[..., None].repeat(3, axis=-1))
             print(f"{name} written to {path}")
+        if denoised:
+            path = os.path.splitext(output)[0] + ".denoised.exr"
+            write_image(path, denoise(buffers, ctx=ctx)["rgb"])
+            print(f"denoised image written to {path}")
     return 0
 
 

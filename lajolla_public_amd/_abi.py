@@ -135,6 +135,17 @@ class LjFeatureStats(C.Structure):
     _fields_ = [("features_ms", C.c_double), ("variance_ms", C.c_double), ("feature_rays", C.c_uint64), ("feature_launches", C.c_uint64)]
 
 
+LJ_DENOISE_DEMODULATE = 1
+
+
+class LjDenoiseArgs(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
+
+
+class LjDenoiseStats(C.Structure):
+    _fields_ = [("denoise_ms", C.c_double), ("launches", C.c_uint64), ("pixels", C.c_uint64)]
+
+
 # the buffers of lj_render_features beside "rgb", in LjFeatureBuffers order, with their channel counts (1: no channel axis)
 FEATURE_CHANNELS = {"rgb": 3, "albedo": 3, "normal": 3, "depth": 1, "alpha": 1, "variance": 3}
 
@@ -243,6 +254,9 @@ SYMBOLS = [
     ("lj_render_features", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.POINTER(LjFeatureBuffers)]),
     ("lj_render_features_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.POINTER(LjFeatureBuffers), C.c_void_p]),
     ("lj_get_feature_stats", C.c_int, [C.c_void_p, C.POINTER(LjFeatureStats)]),
+    ("lj_denoise", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LjFeatureBuffers), C.POINTER(LjDenoiseArgs), C.c_void_p, C.c_void_p]),
+    ("lj_denoise_device", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LjFeatureBuffers), C.POINTER(LjDenoiseArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lj_get_denoise_stats", C.c_int, [C.c_void_p, C.POINTER(LjDenoiseStats)]),
     ("lj_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_occluded", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_get_stats", C.c_int, [C.c_void_p, C.POINTER(LjStats)]),

@@ -36,6 +36,16 @@ void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hi
 int features_grid(uint64_t n_pixels, uint32_t spp, int n_cus);
 void launch_features(const DScene &sc, const DPass &pass, uint32_t n_pixels, uint32_t want, float *albedo, float *normal, float *depth, float *alpha, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
 void launch_resolve_variance(const DPass &pass, uint32_t n_pixels, float *variance, hipStream_t s);
+// denoise.hip: the a-trous filter of lj_denoise over `total` = n * w * h pixels; guide / dyn: one denoise_record_bytes() record per pixel.
+// (ddenoise.h, the rule, is not included here: it switches floating-point contraction off for the rest of a translation unit.)
+struct DenoiseCall { uint32_t has; int32_t iterations; float sigma[4]; };   // has: denoise_has(); iterations and sigma (colour, normal, depth, albedo) as LjDenoiseArgs gives them
+uint32_t denoise_has(bool variance, bool albedo, bool normal, bool depth, bool demodulate);
+int denoise_max_iterations();
+int denoise_iterations(const DenoiseCall &c);   // with the default filled in
+size_t denoise_record_bytes();
+void launch_denoise_pack(uint32_t has, uint64_t total, const float *rgb, const float *variance, const float *albedo, const float *normal, const float *depth, void *guide, void *dyn, hipStream_t s);
+void launch_atrous(const DenoiseCall &c, int n, int w, int h, int iteration, bool lds, const void *guide, const void *dyn_in, void *dyn_out, hipStream_t s);
+void launch_denoise_unpack(uint32_t has, uint64_t total, const void *guide, const void *dyn, float *rgb_out, float *variance_out, hipStream_t s);
 // mega.hip
 size_t mega_smem(const DScene &sc, const ShadeConfig &scfg);
 int mega_blocks_per_cu(const DScene &sc, const ShadeConfig &scfg);
@@ -83,6 +93,11 @@ inline bool mega_enabled() { return env_int("LJ_TUNE_MEGA", 1) != 0; }
 // Read per render and per query: the tests reach several passes per wave-step with it at sizes where the pool would never fill.
 inline uint32_t mega_item_cap_tune() { return (uint32_t)std::max(0, env_int("LJ_TUNE_MEGA_ITEM_CAP", 0)); }
 
+// LJ_TUNE_DENOISE_LDS=k: the first k iterations of lj_denoise (steps 1, 2, .. 1 << (k - 1)) filter from a haloed tile in LDS, the others
+// gather from global memory; 0: all direct.  Clamped to [0, 3] (step 4: a 64 KiB tile); the default is the measured choice of DESIGN.md §3.8.
+static constexpr int kDenoiseLdsDefault = 2, kDenoiseLdsMax = 3;
+inline int denoise_lds_iterations() { return std::min(std::max(env_int("LJ_TUNE_DENOISE_LDS", kDenoiseLdsDefault), 0), kDenoiseLdsMax); }
+
 template <typename T> inline void upload(DevBuf &b, const std::vector<T> &v, hipStream_t s) {
     b.alloc(((std::max<size_t>(v.size(), 1) * sizeof(T)) + 31) & ~(size_t)15);
     if (!v.empty()) HIP_CHECK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
@@ -117,6 +132,11 @@ struct lj_context {
     // lj_render_features: the host variant's five buffers, and the events around a pass's variance and feature launches (recorded in a features call only)
     DevBuf feature_frames;
     hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr, ev_f2 = nullptr;
+    // lj_denoise: the packed records (guide; the two dynamic buffers an iteration ping-pongs between), the host variant's inputs and outputs on
+    // the device, events of its own around a call's launches, and the last call's statistics (the time is read when they are asked for)
+    DevBuf dn_guide, dn_dyn[2], dn_in, dn_out;
+    hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;
+    LjDenoiseStats denoise_stats{}; bool denoise_time_pending = false;
 };
 
 struct lj_scene {
