@@ -359,6 +359,57 @@ int lj_denoise_device(lj_context *ctx, int32_t n, int32_t width, int32_t height,
 typedef struct LjDenoiseStats { double denoise_ms; uint64_t launches, pixels; } LjDenoiseStats;
 int lj_get_denoise_stats(const lj_context *ctx, LjDenoiseStats *out);
 
+/* ---- Adaptive sampling: samples where the error is.  The render runs in rounds: round 0 gives every pixel of the call's share min_spp
+ * samples; after each round the pixels whose relative error — the largest variance of the mean in their 3 x 3 neighbourhood over their squared
+ * brightness — still exceeds target_error^2, and that have room below max_spp, get round_spp more.  The rule — state, merge, error, selection,
+ * seeds, order of the float operations — is spelled out in csrc/device/dadaptive.h (shared by the kernels and a host twin, which agree bit
+ * for bit) and in DESIGN.md 3.9.  Round r renders its list with seed_r = seed + r * 0x9e3779b97f4a7c15 (0 becomes 1) and streams
+ * pixel * k_r + s, so it yields at each listed pixel what lj_render_features(spp = k_r, seed = seed_r) yields there.
+ * Outputs: rgb = the mean over all of a pixel's samples, variance = its squared standard error (0 below two samples), samples = how many it
+ * got; albedo, normal, depth, alpha: the guide buffers of round 0, bit-identical to lj_render_features at spp = min_spp — lj_denoise takes
+ * an adaptive result as it is.  Pixels outside the rank's share or the crop window are 0 in every buffer.
+ * args: max_depth, seed, rank / world_size, the crop window, pool_paths and flags as for lj_render; spp is ignored.
+ * Results are bit-identical from call to call, for any pass size, pool size and kernel plan, and between the host and the device variant.
+ * NOT promised past round 0: invariance under crop or share (the neighbourhood at a share's border differs from the full frame's).
+ * One camera, one device: no camera batches and no device groups (render on each lj_group_scene_member).
+ * LJ_ERR_UNSUPPORTED: rng_mode LJ_RNG_TILE; a scene with one of the five auxiliary integrators.  LJ_ERR_INVALID_ARG: a NULL
+ * LjAdaptiveBuffers or one with all seven pointers NULL; min_spp == 1; max_spp < min_spp; an spp above 2^20; max_rounds > 64; a target_error
+ * that is negative or not finite.  A refused call writes nothing. */
+typedef struct LjAdaptiveArgs {        /* every field: <= 0 for the default; NULL args: all defaults */
+    int32_t min_spp;                   /* samples of round 0; default 16, must not be 1 */
+    int32_t max_spp;                   /* no pixel gets more; default 16 * min_spp, at least min_spp, at most 2^20 */
+    int32_t round_spp;                 /* samples of a later round; default min_spp */
+    int32_t max_rounds;                /* renders of a call, round 0 included; default 16, at most 64 */
+    float target_error;                /* relative standard error to reach; default 0.05; finite, not negative */
+} LjAdaptiveArgs;
+typedef struct LjAdaptiveBuffers {     /* any pointer may be NULL: not wanted */
+    float *rgb;         /* [h][w][3] */
+    float *variance;    /* [h][w][3] */
+    uint32_t *samples;  /* [h][w]    */
+    float *albedo;      /* [h][w][3] */
+    float *normal;      /* [h][w][3] */
+    float *depth;       /* [h][w]    */
+    float *alpha;       /* [h][w]    */
+} LjAdaptiveBuffers;
+/* Blocking; host pointers. */
+int lj_render_adaptive(lj_scene *scene, const LjRenderArgs *args, const LjAdaptiveArgs *adaptive, const LjAdaptiveBuffers *out_host);
+/* Same, into caller-owned DEVICE memory; ordering on `hip_stream` as lj_render_device.  (The call waits once per round, for the length of
+ * the next list.) */
+int lj_render_adaptive_device(lj_scene *scene, const LjRenderArgs *args, const LjAdaptiveArgs *adaptive, const LjAdaptiveBuffers *out_device,
+                              void *hip_stream);
+/* Of the last lj_render_adaptive* call on the scene (zeros after any other render): the renders it ran (round 0 included), the samples it
+ * traced, the length of each round's list, and the device time of the selection and of the merge launches over all rounds.
+ * lj_get_stats after an adaptive call returns the field-wise sums over the rounds' renders. */
+typedef struct LjAdaptiveStats { uint64_t rounds, samples; uint64_t round_pixels[64]; double select_ms, merge_ms; } LjAdaptiveStats;
+int lj_get_adaptive_stats(const lj_scene *scene, LjAdaptiveStats *out);
+/* Test hook: the selection of one round on caller-supplied state of a width x height film — n[h][w], mean[h][w][3], m2[h][w][3] as
+ * dadaptive.h defines them — over pixel_list[n_list] (film pixel indices y * width + x, each at most once), by the very select, scan and
+ * scatter launches a render's rounds run.  selected_out: room for n_list entries; *n_selected: how many were written.  A pure image
+ * operation on a context, like lj_denoise.  Host pointers; blocking.  LJ_ERR_INVALID_ARG: NULL pointers, width or height <= 0, more than
+ * 2^31 pixels, n_list < 0 or above 2^31, a listed pixel outside the film, arguments lj_render_adaptive refuses. */
+int lj_adaptive_select_query(lj_context *ctx, int32_t width, int32_t height, const uint32_t *n, const float *mean, const float *m2,
+                             const LjAdaptiveArgs *adaptive, const uint32_t *pixel_list, int64_t n_list, uint32_t *selected_out, int64_t *n_selected);
+
 /* Per-sample radiance for the crop window: out[((y-y0)*(x1-x0) + (x-x0))*spp + s][3] — one path_tracing()
  * value (path_tracing.h:7-325) per entry, for path-by-path parity tests. */
 int lj_render_samples(lj_scene *scene, const LjRenderArgs *args, float *radiance_host);

@@ -451,6 +451,73 @@ def denoise_stats(ctx):
     return st
 
 
+ADAPTIVE_GUIDES = ("albedo", "normal", "depth", "alpha")
+
+
+def make_adaptive_args(min_spp=0, max_spp=0, round_spp=0, target_error=0.0, max_rounds=0):
+    """LjAdaptiveArgs: 0 (or less) for a default — min_spp 16, max_spp 16 * min_spp, round_spp min_spp, target_error 0.05, max_rounds 16."""
+    a = _abi.LjAdaptiveArgs()
+    a.min_spp, a.max_spp, a.round_spp, a.max_rounds = int(min_spp), int(max_spp), int(round_spp), int(max_rounds)
+    a.target_error = float(target_error)
+    return a
+
+
+def render_adaptive(scene, min_spp=0, max_spp=0, round_spp=0, target_error=0.0, max_rounds=0, guides=False, **kw):
+    """Variance-driven sampling in rounds (lj_render_adaptive): every pixel gets min_spp samples, then the pixels whose relative error still
+    exceeds target_error get round_spp more per round, up to max_spp and max_rounds.  A dict: "rgb" (h, w, 3) float32, "variance" (h, w, 3)
+    float32 — the squared standard error of rgb — and "samples" (h, w) uint32; with guides=True also "albedo", "normal", "depth" and "alpha"
+    of round 0, so that the dict can go to denoise() as it is.  **kw: seed, max_depth, rank / world_size, crop, pool_paths, flags as for
+    render(); spp is ignored."""
+    args = make_args(**kw)
+    aargs = make_adaptive_args(min_spp, max_spp, round_spp, target_error, max_rounds)
+    lead = (scene.info.height, scene.info.width)
+    out, bufs = {}, _abi.LjAdaptiveBuffers()
+    for name in ("rgb", "variance", "samples") + (ADAPTIVE_GUIDES if guides else ()):
+        c, dtype = _abi.ADAPTIVE_BUFFERS[name]
+        out[name] = np.empty(lead + ((c,) if c > 1 else ()), dtype)
+        setattr(bufs, name, out[name].ctypes.data)
+    _check(load_library().lj_render_adaptive(scene._h, C.byref(args), C.byref(aargs), C.byref(bufs)))
+    return out
+
+
+def render_adaptive_device(scene, buffers, stream=None, min_spp=0, max_spp=0, round_spp=0, target_error=0.0, max_rounds=0, **kw):
+    """Same, into caller-owned device memory, ordered on a HIP stream as render_device: `buffers` maps "rgb" / "variance" / "samples" (uint32) /
+    "albedo" / "normal" / "depth" / "alpha" to device pointers of h * w * channels elements; a name left out is not written."""
+    bufs = _abi.LjAdaptiveBuffers()
+    for name, ptr in buffers.items():
+        if name not in _abi.ADAPTIVE_BUFFERS:
+            raise ValueError(f"unknown buffer {name!r}: expected some of {tuple(_abi.ADAPTIVE_BUFFERS)}")
+        setattr(bufs, name, int(ptr) if ptr else None)
+    args = make_args(**kw)
+    aargs = make_adaptive_args(min_spp, max_spp, round_spp, target_error, max_rounds)
+    _check(load_library().lj_render_adaptive_device(scene._h, C.byref(args), C.byref(aargs), C.byref(bufs), C.c_void_p(int(stream or 0))))
+
+
+def adaptive_stats(scene):
+    """LjAdaptiveStats of the scene's last render_adaptive* call (zeros after any other render)."""
+    st = _abi.LjAdaptiveStats()
+    _check(load_library().lj_get_adaptive_stats(scene._h, C.byref(st)))
+    return st
+
+
+def adaptive_select(ctx, n, mean, m2, pixel_list=None, **adaptive):
+    """The selection of one round on given state (lj_adaptive_select_query, a test hook): n (h, w) uint32, mean and m2 (h, w, 3) float32,
+    pixel_list: film pixel indices in the order to keep (None: row-major, the whole film).  Returns the selected list, uint32.
+    **adaptive: min_spp, max_spp, round_spp, target_error, max_rounds."""
+    n = np.ascontiguousarray(n, np.uint32)
+    if n.ndim != 2:
+        raise ValueError("adaptive_select: n must be (h, w)")
+    h, w = n.shape
+    mean, m2 = np.ascontiguousarray(mean, np.float32), np.ascontiguousarray(m2, np.float32)
+    if mean.shape != (h, w, 3) or m2.shape != (h, w, 3):
+        raise ValueError("adaptive_select: mean and m2 must be (h, w, 3)")
+    lst = np.arange(h * w, dtype=np.uint32) if pixel_list is None else np.ascontiguousarray(pixel_list, np.uint32).reshape(-1)
+    out, got = np.empty(max(lst.size, 1), np.uint32), C.c_int64()
+    aargs = make_adaptive_args(**adaptive)
+    _check(load_library().lj_adaptive_select_query(ctx._h, w, h, _vp(n), _vp(mean), _vp(m2), C.byref(aargs), _vp(lst), lst.size, _vp(out), C.byref(got)))
+    return out[:got.value].copy()
+
+
 def render_samples(scene, crop, **kw):
     """Per-sample radiance over a crop window: (crop_h, crop_w, spp, 3) float32 — one path_tracing() value each."""
     args = make_args(crop=crop, **kw)

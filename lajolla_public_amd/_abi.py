@@ -146,6 +146,22 @@ class LjDenoiseStats(C.Structure):
     _fields_ = [("denoise_ms", C.c_double), ("launches", C.c_uint64), ("pixels", C.c_uint64)]
 
 
+class LjAdaptiveArgs(C.Structure):
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("round_spp", C.c_int32), ("max_rounds", C.c_int32), ("target_error", C.c_float)]
+
+
+class LjAdaptiveBuffers(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("variance", C.c_void_p), ("samples", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p)]
+
+
+class LjAdaptiveStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint64), ("samples", C.c_uint64), ("round_pixels", C.c_uint64 * 64), ("select_ms", C.c_double), ("merge_ms", C.c_double)]
+
+
+# the buffers of lj_render_adaptive in LjAdaptiveBuffers order: (channels, numpy dtype name)
+ADAPTIVE_BUFFERS = {"rgb": (3, "float32"), "variance": (3, "float32"), "samples": (1, "uint32"), "albedo": (3, "float32"), "normal": (3, "float32"),
+                    "depth": (1, "float32"), "alpha": (1, "float32")}
+
 # the buffers of lj_render_features beside "rgb", in LjFeatureBuffers order, with their channel counts (1: no channel axis)
 FEATURE_CHANNELS = {"rgb": 3, "albedo": 3, "normal": 3, "depth": 1, "alpha": 1, "variance": 3}
 
@@ -257,6 +273,11 @@ SYMBOLS = [
     ("lj_denoise", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LjFeatureBuffers), C.POINTER(LjDenoiseArgs), C.c_void_p, C.c_void_p]),
     ("lj_denoise_device", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LjFeatureBuffers), C.POINTER(LjDenoiseArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lj_get_denoise_stats", C.c_int, [C.c_void_p, C.POINTER(LjDenoiseStats)]),
+    ("lj_render_adaptive", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.POINTER(LjAdaptiveArgs), C.POINTER(LjAdaptiveBuffers)]),
+    ("lj_render_adaptive_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.POINTER(LjAdaptiveArgs), C.POINTER(LjAdaptiveBuffers), C.c_void_p]),
+    ("lj_get_adaptive_stats", C.c_int, [C.c_void_p, C.POINTER(LjAdaptiveStats)]),
+    ("lj_adaptive_select_query", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LjAdaptiveArgs), C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.POINTER(C.c_int64)]),
     ("lj_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_occluded", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_get_stats", C.c_int, [C.c_void_p, C.POINTER(LjStats)]),

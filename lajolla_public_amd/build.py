@@ -26,7 +26,7 @@ ORACLE_LIB = os.path.join(ROOT, "oracle", "_build", "liblj_oracle_asan.so" if _S
 TWIN_LIB = os.path.join(ROOT, "tests", "twin", "_build", "libljtwin_asan.so" if _SAN else "libljtwin.so")
 
 HOST_SOURCES = ["host/api_host.cpp", "host/scene_xml.cpp", "host/mesh_io.cpp", "host/image_io.cpp", "host/jpeg_decode.cpp", "host/exr_decode.cpp", "host/png_decode.cpp", "host/tga_bmp_decode.cpp", "host/flatten.cpp", "host/bvh.cpp"]
-HIP_SOURCES = ["device/kernels.hip", "device/extend.hip", "device/extend8.hip", "device/volpath.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip"]
+HIP_SOURCES = ["device/kernels.hip", "device/extend.hip", "device/extend8.hip", "device/volpath.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip", "device/adaptive.hip"]
 ARCH = "gfx950"
 
 
@@ -301,6 +301,23 @@ def build_twin_denoise(verbose=True):
     return TWIN_DENOISE_LIB
 
 
+TWIN_ADAPTIVE_LIB = os.path.join(ROOT, "tests", "twin_adaptive", "_build", "libljtwinadaptive_asan.so" if _SAN else "libljtwinadaptive.so")
+
+
+def build_twin_adaptive(verbose=True):
+    """Host build of the rule of lj_render_adaptive (device/dadaptive.h) for the CPU-side tests; the flags of build_twin_denoise, and no scene source."""
+    src = os.path.join(ROOT, "tests", "twin_adaptive", "twin_adaptive.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_ADAPTIVE_LIB), exist_ok=True)
+    if _stale(TWIN_ADAPTIVE_LIB, [src] + _headers()):
+        if verbose:
+            print("[build] compiling the host twin of the adaptive-sampling rule (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2", "-ffp-contract=off"] + _SAN_FLAGS + _host_fma_flag() + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+              "-o", TWIN_ADAPTIVE_LIB, src])
+    return TWIN_ADAPTIVE_LIB
+
+
 def build_reference_subset():
     """oracle/_ref from the reference's own sources — only where /root/reference exists (this container)."""
     script = os.path.join(ROOT, "oracle", "ref_build.sh")
@@ -323,4 +340,5 @@ if __name__ == "__main__":
         build_twin_refit()
         build_twin_features()
         build_twin_denoise()
+        build_twin_adaptive()
     print(LIB)

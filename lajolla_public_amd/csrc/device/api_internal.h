@@ -46,6 +46,17 @@ size_t denoise_record_bytes();
 void launch_denoise_pack(uint32_t has, uint64_t total, const float *rgb, const float *variance, const float *albedo, const float *normal, const float *depth, void *guide, void *dyn, hipStream_t s);
 void launch_atrous(const DenoiseCall &c, int n, int w, int h, int iteration, bool lds, const void *guide, const void *dyn_in, void *dyn_out, hipStream_t s);
 void launch_denoise_unpack(uint32_t has, uint64_t total, const void *guide, const void *dyn, float *rgb_out, float *variance_out, hipStream_t s);
+// adaptive.hip: the kernels of lj_render_adaptive between the renders of its rounds (dadaptive.h, the rule, is not included here either).
+// State of a w x h film: n (one word per pixel), mean and m2 (three floats per pixel).  max_grid > 0 caps a launch's workgroups (LJ_TUNE_ADAPTIVE_GRID).
+struct AdaptiveCall { uint32_t min_spp, max_spp, round_spp, max_rounds; float target_error; };   // LjAdaptiveArgs with the defaults filled in
+int adaptive_resolve(int32_t min_spp, int32_t max_spp, int32_t round_spp, int32_t max_rounds, float target_error, AdaptiveCall &out);   // 0, or what is wrong (dadaptive.h adaptive_params)
+uint64_t adaptive_seed(uint64_t seed0, uint32_t round);
+int adaptive_max_rounds();
+uint32_t adaptive_tiles(uint64_t n_list);   // 256-entry tiles of a list: the words of `counts` and of `offsets`
+void launch_adaptive_merge(const uint32_t *list, uint64_t n_list, uint32_t k, bool init, const float *rgb, const float *variance, uint32_t *n, float *mean, float *m2, int n_cus, int max_grid, hipStream_t s);
+void launch_adaptive_select(const AdaptiveCall &c, int w, int h, const uint32_t *n, const float *mean, const float *m2, const uint32_t *list, uint64_t n_list,
+                            uint8_t *flags, uint32_t *counts, uint32_t *offsets, uint32_t *total, uint32_t *selected, int n_cus, int max_grid, hipStream_t s);
+void launch_adaptive_output(uint64_t n_pixels, const uint32_t *n, const float *mean, const float *m2, float *rgb, float *variance, uint32_t *samples, int n_cus, int max_grid, hipStream_t s);
 // mega.hip
 size_t mega_smem(const DScene &sc, const ShadeConfig &scfg);
 int mega_blocks_per_cu(const DScene &sc, const ShadeConfig &scfg);
@@ -96,6 +107,9 @@ inline uint32_t mega_item_cap_tune() { return (uint32_t)std::max(0, env_int("LJ_
 // LJ_TUNE_DENOISE_LDS=k: the first k iterations of lj_denoise (steps 1, 2, .. 1 << (k - 1)) filter from a haloed tile in LDS, the others
 // gather from global memory; 0: all direct.  Clamped to [0, 3] (step 4: a 64 KiB tile); the default is the measured choice of DESIGN.md §3.8.
 static constexpr int kDenoiseLdsDefault = 2, kDenoiseLdsMax = 3;
+// LJ_TUNE_ADAPTIVE_GRID=n: at most n workgroups per launch of adaptive.hip (0: the CU-count cap alone) — the tests reach several tiles per
+// workgroup with it at small films.  The lists do not depend on it.
+inline int adaptive_max_grid() { return std::max(0, env_int("LJ_TUNE_ADAPTIVE_GRID", 0)); }
 inline int denoise_lds_iterations() { return std::min(std::max(env_int("LJ_TUNE_DENOISE_LDS", kDenoiseLdsDefault), 0), kDenoiseLdsMax); }
 
 template <typename T> inline void upload(DevBuf &b, const std::vector<T> &v, hipStream_t s) {
@@ -137,6 +151,10 @@ struct lj_context {
     DevBuf dn_guide, dn_dyn[2], dn_in, dn_out;
     hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;
     LjDenoiseStats denoise_stats{}; bool denoise_time_pending = false;
+    // lj_render_adaptive: the state of the film (n, mean, m2), a round's rgb and variance frames, the call's list and the selected one, the
+    // selection's flags and tile counts / offsets / total, the host variant's three outputs, and events around a round's merge and selection
+    DevBuf ad_n, ad_mean, ad_m2, ad_rgb, ad_var, ad_list, ad_sel, ad_flags, ad_scan, ad_out;
+    hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr, ev_a2 = nullptr;
 };
 
 struct lj_scene {
@@ -154,6 +172,7 @@ struct lj_scene {
     std::vector<int64_t> shape_first_gprim;   // global primitive id of each shape's first primitive (shape order, then triangle order)
     LjStats stats{};
     LjFeatureStats feature_stats{};   // of the last lj_render_features* call; zeros after any other render
+    LjAdaptiveStats adaptive_stats{};   // of the last lj_render_adaptive* call; zeros after any other render
 };
 
 inline void set_device(lj_context *ctx) { HIP_CHECK(hipSetDevice(ctx->device)); }

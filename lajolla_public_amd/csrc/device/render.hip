@@ -583,6 +583,7 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
     set_device(sc->ctx);
     sc->stats = LjStats{};
     sc->feature_stats = LjFeatureStats{};
+    sc->adaptive_stats = LjAdaptiveStats{};
     if (plan.pixels->empty()) return;
     if (sc->flat.integrator < LJ_INTEGRATOR_PATH) return render_aux(sc, plan, rgb_dev, samples_host, stream);
     ljd::DScene ds = sc->dscene;   // the scene as the plan's kernels see it
