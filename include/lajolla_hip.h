@@ -267,6 +267,50 @@ int lj_scene_set_camera(lj_scene *scene, const LjCamera *camera);
  * generate_ms = the host time of the re-derivation.  Device groups: apply the update to each lj_group_scene_member. */
 int lj_scene_update_geometry(lj_scene *scene, const LjSceneDesc *desc);
 
+/* ---- rebuilding the trees of a moved scene
+ * Rebuilds the BVH4 and the BVH8 of an uploaded scene for the geometry that is on the device now, after any number of
+ * lj_scene_update_geometry calls: a linear BVH (Morton order of the padded primitive boxes, Karras' radix tree, leaves of at most four
+ * primitives) built on the device, collapsed into the two wide trees by the code lj_scene_upload runs, then refitted by the kernels of
+ * lj_scene_update_geometry — so the stored boxes are by definition the refit of the new topology, and a later update with unchanged
+ * positions changes no byte.
+ * Kept: primitive records, light tables, materials, media, camera, mip pyramids, shade configuration.  Replaced: both trees, the
+ * leaf-ordered primitives and the leaf order (now a permutation of the primitives: a linear BVH has no split references), the refit
+ * level tables, both depths.  Recomputed: the extend kernels' launch plan, by the function lj_scene_upload calls — it reads LJ_TUNE_*
+ * again, as at upload (LJ_TUNE_BVH8, LJ_TUNE_NODE8_STRIDE, LJ_TUNE_REFILL, LJ_TUNE_MINDESC: keep them set across both calls).
+ * lj_scene_info, lj_scene_read_bvh and a later lj_scene_update_geometry see the new trees.  Hits and per-sample radiance do not depend on
+ * the tree (see above): after a rebuild they are bit-identical to a fresh lj_scene_upload of the same description.
+ *
+ * A scene with a leaf table (at most 32 leaves and 256 primitives: every ray tests every leaf box, there is no tree to degrade, and the
+ * underfilled leaves of a linear BVH would push the scene out of that plan) and an empty scene are left untouched: the call returns
+ * LJ_OK with LjRebuildStats::rebuilt = 0.
+ *
+ * LJ_ERR_INVALID_ARG: a null scene or one that is not live.  LJ_ERR_UNSUPPORTED: the emitted BVH4 is deeper than the traversal stack
+ * (40 levels), or the 24-bit node / 30-bit leaf index limits are hit.  Every check runs before the first write to the scene: a refused
+ * call leaves it as it was.
+ * Blocking, ordered on the context's stream.  lj_get_stats after the call: render_ms = device time, generate_ms = host time, every
+ * other field 0.
+ *
+ * Refit, rebuild or re-upload (measured, DESIGN.md section 3.10: 60 K - 66 K triangles, 16 spp, one MI355X): an update costs 4 - 5 ms, update
+ * plus rebuild 12 - 15 ms, a re-upload 340 - 790 ms; a frame on the refitted tree takes 1.4 - 5.8 times the freshly built tree's time, on the
+ * rebuilt tree 1.15 - 1.55 times.  So: refit alone for a scene with a leaf table (nothing else happens anyway) and for a pose that is
+ * rendered for less than the rebuild's 8 - 10 ms; rebuild after the update whenever more than that is rendered per pose — it paid for
+ * itself within one 16-spp frame in every case measured, at amplitude 0 too, because it also sheds what the first refit lost (the
+ * clipping of the upload's split leaves); re-upload only for a pose that is rendered for seconds, where the last 15 - 55 % are worth
+ * half a second of host time. */
+int lj_scene_rebuild_bvh(lj_scene *scene);
+/* Of the scene's last lj_scene_rebuild_bvh (zeros before the first): rebuilt 1 or 0 (the no-op above); primitives, leaves, nodes and
+ * depths of the trees as they stand; build_ms = the device's linear BVH (boxes, codes, sort, hierarchy, fit) and its readback,
+ * emit_ms = the host's collapse into the wide trees and level tables, refit_ms = upload of the trees and the refit launches. */
+typedef struct LjRebuildStats { uint64_t rebuilt, n_prims, n_leaves, n_nodes4, n_nodes8; int32_t depth4, depth8;
+                                double build_ms, emit_ms, refit_ms; } LjRebuildStats;
+int lj_get_rebuild_stats(const lj_scene *scene, LjRebuildStats *out);
+/* Test hook, a pure function on a context: the device's linear BVH over n boxes (float[n][2][3]: lo, hi; finite, lo <= hi, else
+ * LJ_ERR_INVALID_ARG).  order_out[n]: sorted position -> box.  nodes_out: the reachable nodes, breadth-first from the root (node 0); an
+ * inner node has left / right >= 0, a leaf has both -1 and holds order_out[first .. first + count), count <= 4.  *n_nodes = their number
+ * (0 for n = 0); nodes_out may be null to ask for it, else capacity (in nodes) must hold them. */
+typedef struct LjBinaryNode { float lo[3], hi[3]; int32_t left, right, first, count; } LjBinaryNode;   /* 40 bytes */
+int lj_bvh_build_query(lj_context *ctx, int64_t n, const float *boxes, int32_t *order_out, LjBinaryNode *nodes_out, int64_t capacity, int64_t *n_nodes);
+
 /* Readback of an acceleration structure as it stands on the device, for tests: which = 0 the BVH4 (128-byte DNode4 records), 1 the BVH8
  * (80-byte DNode8 records, packed whatever their stride on the device), 2 a tiny scene's leaf table (32-byte DScanLeaf records; none for
  * other scenes).  *bytes = the size of the structure; out_host may be null to ask for it, else capacity_bytes must hold it. */
@@ -500,10 +544,11 @@ typedef struct LjMediumQuery { int32_t medium_id; float p[3], org[3], dir[3], tf
 typedef struct LjMediumResult { float sigma_s[3], sigma_a[3], majorant[3]; } LjMediumResult;
 int lj_medium_queries(lj_scene *scene, int64_t n, const LjMediumQuery *queries_host, LjMediumResult *results_host);
 
-/* Counters of the last lj_render* call — or of the last lj_intersect, lj_occluded or lj_scene_update_geometry, which overwrite them too:
+/* Counters of the last lj_render* call — or of the last lj_intersect, lj_occluded, lj_scene_update_geometry or lj_scene_rebuild_bvh, which
+ * overwrite them too:
  * a ray query leaves render_ms = the query kernel's device time, rays_closest or rays_shadow = n, and mega_launches = 1 or
  * extend_launches = 1 for the route that answered (a tiny scene's leaf scan, or the BVH traversal); an update leaves render_ms and
- * generate_ms (see lj_scene_update_geometry).  Every other field is then 0.  Read the counters of a render before the next such call. */
+ * generate_ms (see lj_scene_update_geometry), and so does a rebuild (see lj_scene_rebuild_bvh).  Every other field is then 0.  Read the counters of a render before the next such call. */
 typedef struct LjStats {
     uint64_t samples;          /* camera samples traced (LJ_RNG_TILE: those of every tile walked, outside a crop window too) */
     uint64_t bounce_iterations;/* sum over samples of executed iterations of the loop at path_tracing.h:66 (K) */

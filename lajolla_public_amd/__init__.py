@@ -195,14 +195,27 @@ class Scene:
         _check(lib.lj_scene_info(self._h, C.byref(info)))
         self.info = info
 
-    def update_geometry(self, host_scene_or_desc):
+    def update_geometry(self, host_scene_or_desc, rebuild=False):
         """The scene with its vertices moved: `host_scene_or_desc` is the uploaded description with other positions, normals or sphere
         positions / radii (HostScene.positions_view()); everything derived from them is re-derived and the BVHs are refitted on the device,
         nothing else is rebuilt (lj_scene_update_geometry).  Later renders and queries see the new geometry, bit-identical to a fresh
-        Scene of the same description.  A refused update (LajollaError, LJ_ERR_INVALID_ARG) leaves the scene as it was."""
+        Scene of the same description.  A refused update (LajollaError, LJ_ERR_INVALID_ARG) leaves the scene as it was.
+        rebuild=True: rebuild_bvh() after the update."""
         lib = load_library()
         desc_ptr = host_scene_or_desc.desc_ptr if isinstance(host_scene_or_desc, HostScene) else C.pointer(host_scene_or_desc)
         _check(lib.lj_scene_update_geometry(self._h, desc_ptr))
+        if rebuild:
+            _check(lib.lj_scene_rebuild_bvh(self._h))
+        info = LjSceneInfo()
+        _check(lib.lj_scene_info(self._h, C.byref(info)))
+        self.info = info
+
+    def rebuild_bvh(self):
+        """Rebuild both trees on the device for the geometry as it stands there (lj_scene_rebuild_bvh): a linear BVH in place of the
+        refitted trees.  Hits and per-sample radiance do not change.  A leaf-scan scene (at most 32 leaves and 256 primitives) and an
+        empty scene are left as they are (rebuild_stats(scene).rebuilt == 0).  LJ_TUNE_* are read again, as at upload."""
+        lib = load_library()
+        _check(lib.lj_scene_rebuild_bvh(self._h))
         info = LjSceneInfo()
         _check(lib.lj_scene_info(self._h, C.byref(info)))
         self.info = info
@@ -218,6 +231,28 @@ def read_bvh(scene, which):
     if n.value:
         _check(lib.lj_scene_read_bvh(scene._h, int(which), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
     return out
+
+
+def rebuild_stats(scene):
+    """LjRebuildStats of the scene's last rebuild_bvh() (zeros before the first)."""
+    st = _abi.LjRebuildStats()
+    _check(load_library().lj_get_rebuild_stats(scene._h, C.byref(st)))
+    return st
+
+
+BINARY_NODE = np.dtype([("lo", np.float32, 3), ("hi", np.float32, 3), ("left", np.int32), ("right", np.int32), ("first", np.int32), ("count", np.int32)])
+
+
+def bvh_build_query(ctx, boxes):
+    """The device's linear BVH over boxes (n, 2, 3) float32 — lo, hi — (lj_bvh_build_query, a test hook): (order, nodes); order[i] is the
+    box at sorted position i, nodes a BINARY_NODE array, breadth-first from the root."""
+    boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 2, 3)
+    n = boxes.shape[0]
+    order = np.zeros(n, np.int32)
+    nodes = np.zeros(max(2 * n, 1), BINARY_NODE)
+    got = C.c_int64()
+    _check(load_library().lj_bvh_build_query(ctx._h, n, boxes.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p), nodes.ctypes.data_as(C.c_void_p), nodes.size, C.byref(got)))
+    return order, nodes[:got.value].copy()
 
 
 def make_args(spp=0, max_depth=None, rank=0, world_size=1, crop=None, pool_paths=0, seed=0, flags=0, rng_mode=_abi.LJ_RNG_SAMPLE):

@@ -158,6 +158,15 @@ class LjAdaptiveStats(C.Structure):
     _fields_ = [("rounds", C.c_uint64), ("samples", C.c_uint64), ("round_pixels", C.c_uint64 * 64), ("select_ms", C.c_double), ("merge_ms", C.c_double)]
 
 
+class LjRebuildStats(C.Structure):
+    _fields_ = [("rebuilt", C.c_uint64), ("n_prims", C.c_uint64), ("n_leaves", C.c_uint64), ("n_nodes4", C.c_uint64), ("n_nodes8", C.c_uint64),
+                ("depth4", C.c_int32), ("depth8", C.c_int32), ("build_ms", C.c_double), ("emit_ms", C.c_double), ("refit_ms", C.c_double)]
+
+
+class LjBinaryNode(C.Structure):
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("left", C.c_int32), ("right", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
+
+
 # the buffers of lj_render_adaptive in LjAdaptiveBuffers order: (channels, numpy dtype name)
 ADAPTIVE_BUFFERS = {"rgb": (3, "float32"), "variance": (3, "float32"), "samples": (1, "uint32"), "albedo": (3, "float32"), "normal": (3, "float32"),
                     "depth": (1, "float32"), "alpha": (1, "float32")}
@@ -265,6 +274,9 @@ SYMBOLS = [
     ("lj_scene_set_camera", C.c_int, [C.c_void_p, C.POINTER(LjCamera)]),
     ("lj_scene_update_geometry", C.c_int, [C.c_void_p, C.POINTER(LjSceneDesc)]),
     ("lj_scene_read_bvh", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("lj_scene_rebuild_bvh", C.c_int, [C.c_void_p]),
+    ("lj_get_rebuild_stats", C.c_int, [C.c_void_p, C.POINTER(LjRebuildStats)]),
+    ("lj_bvh_build_query", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("lj_render_views", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p]),
     ("lj_render_views_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p, C.c_void_p]),
     ("lj_render_features", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.POINTER(LjFeatureBuffers)]),

@@ -26,7 +26,7 @@ ORACLE_LIB = os.path.join(ROOT, "oracle", "_build", "liblj_oracle_asan.so" if _S
 TWIN_LIB = os.path.join(ROOT, "tests", "twin", "_build", "libljtwin_asan.so" if _SAN else "libljtwin.so")
 
 HOST_SOURCES = ["host/api_host.cpp", "host/scene_xml.cpp", "host/mesh_io.cpp", "host/image_io.cpp", "host/jpeg_decode.cpp", "host/exr_decode.cpp", "host/png_decode.cpp", "host/tga_bmp_decode.cpp", "host/flatten.cpp", "host/bvh.cpp"]
-HIP_SOURCES = ["device/kernels.hip", "device/extend.hip", "device/extend8.hip", "device/volpath.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip", "device/adaptive.hip"]
+HIP_SOURCES = ["device/kernels.hip", "device/extend.hip", "device/extend8.hip", "device/volpath.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip", "device/adaptive.hip", "device/rebuild.hip"]
 ARCH = "gfx950"
 
 
@@ -318,6 +318,25 @@ def build_twin_adaptive(verbose=True):
     return TWIN_ADAPTIVE_LIB
 
 
+TWIN_REBUILD_LIB = os.path.join(ROOT, "tests", "twin_rebuild", "_build", "libljtwinrebuild_asan.so" if _SAN else "libljtwinrebuild.so")
+
+
+def build_twin_rebuild(verbose=True):
+    """Host twin of lj_scene_rebuild_bvh (the build rule of device/drebuild.h, emit_wide, and the twin of the geometry update it includes) for
+    the CPU-side tests; the flags of build_twin_refit."""
+    src = os.path.join(ROOT, "tests", "twin_rebuild", "twin_rebuild.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_REBUILD_LIB), exist_ok=True)
+    deps = [src, os.path.join(ROOT, "tests", "twin_refit", "twin_refit.cpp")] + _headers() + [os.path.join(CSRC, s) for s in ("host/flatten.cpp", "host/bvh.cpp")]
+    if _stale(TWIN_REBUILD_LIB, deps):
+        if verbose:
+            print("[build] compiling the host twin of the BVH rebuild (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2", "-ffp-contract=off"] + _SAN_FLAGS + _host_fma_flag() + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+              "-o", TWIN_REBUILD_LIB, src, os.path.join(CSRC, "host/flatten.cpp"), os.path.join(CSRC, "host/bvh.cpp"), "-lpthread"])
+    return TWIN_REBUILD_LIB
+
+
 def build_reference_subset():
     """oracle/_ref from the reference's own sources — only where /root/reference exists (this container)."""
     script = os.path.join(ROOT, "oracle", "ref_build.sh")
@@ -341,4 +360,5 @@ if __name__ == "__main__":
         build_twin_features()
         build_twin_denoise()
         build_twin_adaptive()
+        build_twin_rebuild()
     print(LIB)

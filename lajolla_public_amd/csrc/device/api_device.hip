@@ -41,6 +41,82 @@ void render_frame(lj_scene *scene, RenderPlan plan, const std::vector<ljd::DCame
     if (caller) { HIP_CHECK(hipEventRecord(ctx->ev_caller, s)); HIP_CHECK(hipStreamWaitEvent(caller, ctx->ev_caller, 0)); }
 }
 
+
+// The trees of scene->flat onto the device, for lj_scene_upload and lj_scene_rebuild_bvh alike: the nodes of both trees (LJ_TUNE_NODE8_STRIDE
+// read here) and the leaf-ordered primitives, what the DScene holds of them, the depth check, and the extend kernels' launch plan with its
+// two overrides.  scene->dscene holds everything else already.  Returns with the copies done.
+void install_trees(lj_scene *sc, hipStream_t s) {
+    lj::FlatScene &F = sc->flat;
+    if (F.bvh_depth > ljd::max_stack_depth())
+        throw LjError(LJ_ERR_INTERNAL, "BVH depth " + std::to_string(F.bvh_depth) + " exceeds the traversal stack");
+    upload(sc->nodes, F.nodes, s);
+    // BVH8 nodes: 80 bytes each; LJ_TUNE_NODE8_STRIDE=128 lays them out one per 128-byte cache line (a node then never straddles two lines)
+    const int node8_stride = env_int("LJ_TUNE_NODE8_STRIDE", 0) >= 128 ? 128 : (int)sizeof(ljd::DNode8);
+    std::vector<unsigned char> nodes8_padded;
+    if (node8_stride == (int)sizeof(ljd::DNode8)) upload(sc->nodes8, F.nodes8, s);
+    else {
+        nodes8_padded.assign(F.nodes8.size() * (size_t)node8_stride, 0);
+        for (size_t i = 0; i < F.nodes8.size(); i++) memcpy(&nodes8_padded[i * (size_t)node8_stride], &F.nodes8[i], sizeof(ljd::DNode8));
+        upload(sc->nodes8, nodes8_padded, s);
+    }
+    upload(sc->leaf_prims, F.leaf_prims, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    ljd::DScene &d = sc->dscene;
+    d.nodes = (const ljd::DNode4 *)sc->nodes.p; d.n_nodes = (int32_t)F.nodes.size();
+    d.nodes8 = (const ljd::DNode8 *)sc->nodes8.p; d.n_nodes8 = (int32_t)F.nodes8.size(); d.node8_stride = node8_stride;
+    d.leaf_prims = (const ljd::DPrim *)sc->leaf_prims.p; d.n_prims = (int32_t)F.leaf_prims.size();
+    sc->ecfg = ljd::extend_config((int)F.nodes.size(), (int)F.leaf_prims.size(), F.bvh_depth, (int)F.n_spheres, (int)F.nodes8.size(), F.bvh8_depth, /* open scene: */ F.envmap_light_id >= 0);
+    sc->ecfg.refill_min = (uint32_t)env_int("LJ_TUNE_REFILL", (int)sc->ecfg.refill_min);
+    sc->ecfg.min_descending = (uint32_t)env_int("LJ_TUNE_MINDESC", (int)sc->ecfg.min_descending);
+}
+
+// The refit launches over the scene's level tables (the leaf table first, then each tree from its deepest level up), and the copy of the
+// refitted nodes into the host's (lj_scene_info and the tests read it); the caller waits for the stream.
+void refit_launches(lj_scene *scene, hipStream_t s) {
+    const lj::FlatScene &F = scene->flat;
+    const ljd::DPrim *lp = (const ljd::DPrim *)scene->leaf_prims.p; const ljd::DSphere *sp = (const ljd::DSphere *)scene->spheres.p;
+    if (!F.scan_leaves.empty()) ljd::launch_refit_scan((ljd::DScanLeaf *)scene->scan_leaves.p, lp, sp, F.n_scan_used, s);
+    for (size_t l = F.level4_first.size() - 1; l-- > 0;)
+        ljd::launch_refit4((ljd::DNode4 *)scene->nodes.p, scene->refit_box4.p, lp, sp, (const int32_t *)scene->refit_levels4.p + F.level4_first[l], F.level4_first[l + 1] - F.level4_first[l], s);
+    const int stride8 = scene->dscene.node8_stride;
+    for (size_t l = F.level8_first.size() - 1; l-- > 0;)
+        ljd::launch_refit8(scene->nodes8.p, stride8, scene->refit_box8.p, lp, sp, (const int32_t *)scene->refit_levels8.p + F.level8_first[l], F.level8_first[l + 1] - F.level8_first[l], s);
+    HIP_CHECK(hipGetLastError());
+}
+void read_back_nodes(lj_scene *scene, hipStream_t s) {
+    lj::FlatScene &F = scene->flat;
+    const int stride8 = scene->dscene.node8_stride;
+    HIP_CHECK(hipMemcpyAsync(F.nodes.data(), scene->nodes.p, F.nodes.size() * sizeof(ljd::DNode4), hipMemcpyDeviceToHost, s));
+    if (stride8 == (int)sizeof(ljd::DNode8)) HIP_CHECK(hipMemcpyAsync(F.nodes8.data(), scene->nodes8.p, F.nodes8.size() * sizeof(ljd::DNode8), hipMemcpyDeviceToHost, s));
+    else HIP_CHECK(hipMemcpy2DAsync(F.nodes8.data(), sizeof(ljd::DNode8), scene->nodes8.p, (size_t)stride8, sizeof(ljd::DNode8), F.nodes8.size(), hipMemcpyDeviceToHost, s));
+    if (!F.scan_leaves.empty()) HIP_CHECK(hipMemcpyAsync(F.scan_leaves.data(), scene->scan_leaves.p, F.scan_leaves.size() * sizeof(ljd::DScanLeaf), hipMemcpyDeviceToHost, s));
+}
+// the per-node box scratch and the level tables of a refit, for the trees as they stand
+void alloc_refit_tables(lj_scene *scene, hipStream_t s) {
+    const lj::FlatScene &F = scene->flat;
+    const size_t bb = ljd::refit_box_bytes();
+    scene->refit_box4.alloc(std::max<size_t>(F.nodes.size(), 1) * bb); scene->refit_box8.alloc(std::max<size_t>(F.nodes8.size(), 1) * bb);
+    upload(scene->refit_levels4, F.levels4, s); upload(scene->refit_levels8, F.levels8, s);
+}
+
+static_assert(sizeof(LjBinaryNode) == sizeof(lj::BinaryNode) && sizeof(LjBinaryNode) == 40, "LjBinaryNode must be 40 bytes");
+
+// The device's linear BVH over the n boxes in w.boxes: order and the compacted binary tree on the host.  Waits for the stream.
+std::vector<lj::BinaryNode> build_binary_tree(const ljd::RebuildWork &w, int n, hipStream_t s, std::vector<int> &order) {
+    ljd::launch_rebuild(w, n, s);
+    HIP_CHECK(hipGetLastError());
+    std::vector<float> boxes((size_t)n * 6);
+    std::vector<int32_t> order32((size_t)n);
+    std::vector<unsigned char> raw((size_t)std::max(n - 1, 0) * ljd::rebuild_node_bytes());
+    HIP_CHECK(hipMemcpyAsync(boxes.data(), w.boxes, boxes.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(order32.data(), w.order, order32.size() * 4, hipMemcpyDeviceToHost, s));
+    if (!raw.empty()) HIP_CHECK(hipMemcpyAsync(raw.data(), w.nodes, raw.size(), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (int32_t g : order32) if (g < 0 || g >= n) throw LjError(LJ_ERR_INTERNAL, "the device's sort returned an index outside the primitives");
+    order.assign(order32.begin(), order32.end());
+    return lj::compact_radix_tree(raw.data(), boxes.data(), order32.data(), n);
+}
+
 } // namespace
 
 extern "C" {
@@ -101,17 +177,7 @@ int lj_scene_upload(lj_context *ctx, const LjSceneDesc *desc, lj_scene **out) {
         sc->flat = lj::flatten_scene(*desc);
         lj::FlatScene &F = sc->flat;
         hipStream_t s = ctx->stream;
-        upload(sc->nodes, F.nodes, s);
-        // BVH8 nodes: 80 bytes each; LJ_TUNE_NODE8_STRIDE=128 lays them out one per 128-byte cache line (a node then never straddles two lines)
-        const int node8_stride = env_int("LJ_TUNE_NODE8_STRIDE", 0) >= 128 ? 128 : (int)sizeof(ljd::DNode8);
-        std::vector<unsigned char> nodes8_padded;
-        if (node8_stride == (int)sizeof(ljd::DNode8)) upload(sc->nodes8, F.nodes8, s);
-        else {
-            nodes8_padded.assign(F.nodes8.size() * (size_t)node8_stride, 0);
-            for (size_t i = 0; i < F.nodes8.size(); i++) memcpy(&nodes8_padded[i * (size_t)node8_stride], &F.nodes8[i], sizeof(ljd::DNode8));
-            upload(sc->nodes8, nodes8_padded, s);
-        }
-        upload(sc->leaf_prims, F.leaf_prims, s); upload(sc->prims, F.prims, s); upload(sc->spheres, F.spheres, s);
+        upload(sc->prims, F.prims, s); upload(sc->spheres, F.spheres, s);
         upload(sc->materials, F.materials, s); upload(sc->lights, F.lights, s); upload(sc->light_cdf, F.light_cdf, s);
         upload(sc->light_tris, F.light_tris, s); upload(sc->light_tri_cdf, F.light_tri_cdf, s);
         upload(sc->images3, F.images3, s); upload(sc->images1, F.images1, s); upload(sc->texels, F.texels, s); upload(sc->env_tables, F.env_tables, s);
@@ -119,7 +185,7 @@ int lj_scene_upload(lj_context *ctx, const LjSceneDesc *desc, lj_scene **out) {
         upload(sc->scan_leaves, F.scan_leaves, s);
         HIP_CHECK(hipStreamSynchronize(s));
         ljd::DScene d = F.host_view();
-        d.nodes = (const ljd::DNode4 *)sc->nodes.p; d.nodes8 = (const ljd::DNode8 *)sc->nodes8.p; d.node8_stride = node8_stride; d.leaf_prims = (const ljd::DPrim *)sc->leaf_prims.p; d.prims = (const ljd::DPrimShade *)sc->prims.p;
+        d.prims = (const ljd::DPrimShade *)sc->prims.p;
         d.spheres = (const ljd::DSphere *)sc->spheres.p; d.materials = (const ljd::DMaterial *)sc->materials.p; d.lights = (const ljd::DLight *)sc->lights.p;
         d.light_cdf = (const float *)sc->light_cdf.p; d.light_tris = (const ljd::DLightTri *)sc->light_tris.p; d.light_tri_cdf = (const float *)sc->light_tri_cdf.p;
         d.images3 = (const ljd::DImage *)sc->images3.p; d.images1 = (const ljd::DImage *)sc->images1.p; d.texels = (const float *)sc->texels.p; d.env_tables = (const float *)sc->env_tables.p; d.env_marg = d.env_tables + F.env_marg_first;
@@ -130,11 +196,7 @@ int lj_scene_upload(lj_context *ctx, const LjSceneDesc *desc, lj_scene **out) {
             for (int si = 0; si < desc->n_shapes; si++) { sc->shape_first_gprim.push_back(g); g += desc->shapes[si].kind == LJ_SHAPE_SPHERE ? 1 : desc->shapes[si].n_triangles; }
             sc->shape_first_gprim.push_back(g);
         }
-        if (F.bvh_depth > ljd::max_stack_depth())
-            throw LjError(LJ_ERR_INTERNAL, "BVH depth " + std::to_string(F.bvh_depth) + " exceeds the traversal stack");
-        sc->ecfg = ljd::extend_config((int)F.nodes.size(), (int)F.leaf_prims.size(), F.bvh_depth, (int)F.n_spheres, (int)F.nodes8.size(), F.bvh8_depth, /* open scene: */ F.envmap_light_id >= 0);
-        sc->ecfg.refill_min = (uint32_t)env_int("LJ_TUNE_REFILL", (int)sc->ecfg.refill_min);
-        sc->ecfg.min_descending = (uint32_t)env_int("LJ_TUNE_MINDESC", (int)sc->ecfg.min_descending);
+        install_trees(sc.get(), s);
         sc->scfg = ljd::shade_config(F.prims.size(), F.materials.size(), F.lights.size(), F.light_tris.size(), F.light_tri_cdf.size(), F.images3.size(), F.images1.size(), (size_t)F.env_marg_count);
         {   // which Material / Texture / Light alternatives the scene holds decides the shade kernel instantiation
             uint32_t kinds = 0; bool textured = false, sphere_lights = false;
@@ -205,36 +267,107 @@ int lj_scene_update_geometry(lj_scene *scene, const LjSceneDesc *desc) {
         lj_context *ctx = scene->ctx;
         set_device(ctx);
         hipStream_t s = ctx->stream;
-        const size_t bb = ljd::refit_box_bytes();
-        if (!scene->refit_box4.p) {
-            scene->refit_box4.alloc(std::max<size_t>(F.nodes.size(), 1) * bb); scene->refit_box8.alloc(std::max<size_t>(F.nodes8.size(), 1) * bb);
-            upload(scene->refit_levels4, F.levels4, s); upload(scene->refit_levels8, F.levels8, s);
-        }
+        if (!scene->refit_box4.p) alloc_refit_tables(scene, s);
         // ---- device, in stream order: the tables, then the boxes of the three structures from the new leaf-ordered primitives
         HIP_CHECK(hipEventRecord(ctx->ev_begin, s));
         auto put = [&](DevBuf &b, const auto &v) { HIP_CHECK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, s)); };
         put(scene->leaf_prims, U.leaf_prims); put(scene->prims, U.prims); put(scene->spheres, U.spheres); put(scene->light_tris, U.light_tris);
         put(scene->light_tri_cdf, U.light_tri_cdf); put(scene->lights, U.lights); put(scene->light_cdf, U.light_cdf);
-        const ljd::DPrim *lp = (const ljd::DPrim *)scene->leaf_prims.p; const ljd::DSphere *sp = (const ljd::DSphere *)scene->spheres.p;
-        if (!F.scan_leaves.empty()) ljd::launch_refit_scan((ljd::DScanLeaf *)scene->scan_leaves.p, lp, sp, F.n_scan_used, s);
-        for (size_t l = F.level4_first.size() - 1; l-- > 0;)
-            ljd::launch_refit4((ljd::DNode4 *)scene->nodes.p, scene->refit_box4.p, lp, sp, (const int32_t *)scene->refit_levels4.p + F.level4_first[l], F.level4_first[l + 1] - F.level4_first[l], s);
-        const int stride8 = scene->dscene.node8_stride;
-        for (size_t l = F.level8_first.size() - 1; l-- > 0;)
-            ljd::launch_refit8(scene->nodes8.p, stride8, scene->refit_box8.p, lp, sp, (const int32_t *)scene->refit_levels8.p + F.level8_first[l], F.level8_first[l + 1] - F.level8_first[l], s);
-        HIP_CHECK(hipGetLastError());
+        refit_launches(scene, s);
         HIP_CHECK(hipEventRecord(ctx->ev_end, s));
         // the host copy of the nodes follows the device's (lj_scene_info and the tests read it)
-        HIP_CHECK(hipMemcpyAsync(F.nodes.data(), scene->nodes.p, F.nodes.size() * sizeof(ljd::DNode4), hipMemcpyDeviceToHost, s));
-        if (stride8 == (int)sizeof(ljd::DNode8)) HIP_CHECK(hipMemcpyAsync(F.nodes8.data(), scene->nodes8.p, F.nodes8.size() * sizeof(ljd::DNode8), hipMemcpyDeviceToHost, s));
-        else HIP_CHECK(hipMemcpy2DAsync(F.nodes8.data(), sizeof(ljd::DNode8), scene->nodes8.p, (size_t)stride8, sizeof(ljd::DNode8), F.nodes8.size(), hipMemcpyDeviceToHost, s));
-        if (!F.scan_leaves.empty()) HIP_CHECK(hipMemcpyAsync(F.scan_leaves.data(), scene->scan_leaves.p, F.scan_leaves.size() * sizeof(ljd::DScanLeaf), hipMemcpyDeviceToHost, s));
+        read_back_nodes(scene, s);
         HIP_CHECK(hipStreamSynchronize(s));
         const float ms = elapsed_ms(ctx->ev_begin, ctx->ev_end);
         lj::commit_update(F, std::move(U));
         scene->dscene.eps = (float)F.shadow_epsilon;
         // LjStats of an update: render_ms = device time (copies of the tables and the refit launches), generate_ms = host time of the re-derivation
         scene->stats = LjStats{}; scene->stats.render_ms = ms; scene->stats.generate_ms = host_ms;
+    });
+}
+
+int lj_scene_rebuild_bvh(lj_scene *scene) {
+    return lj::guard([&]() {
+        if (!scene) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_rebuild_bvh: null scene");
+        if (!scene_is_live(scene)) throw LjError(LJ_ERR_INVALID_ARG, "lj_scene_rebuild_bvh: not an uploaded scene (destroyed?)");
+        lj::FlatScene &F = scene->flat;
+        auto tree_stats = [&](uint64_t rebuilt) {
+            LjRebuildStats r{};
+            r.rebuilt = rebuilt; r.n_prims = F.prims.size(); r.n_nodes4 = F.nodes.size(); r.n_nodes8 = F.nodes8.size(); r.depth4 = F.bvh_depth; r.depth8 = F.bvh8_depth;
+            for (const ljd::DNode4 &nd : F.nodes) for (int k = 0; k < 4; k++) if (nd.lox[k] <= nd.hix[k] && nd.child[k] < 0) r.n_leaves++;
+            return r;
+        };
+        const size_t n_prims = F.prims.size();
+        if (!F.scan_leaves.empty() || n_prims == 0 || F.leaf_prims.empty()) {   // a leaf-scan scene or an empty one: nothing to rebuild
+            scene->rebuild_stats = tree_stats(0); scene->stats = LjStats{};
+            return;
+        }
+        if ((long long)n_prims * 8 >= (1ll << 30)) throw LjError(LJ_ERR_UNSUPPORTED, "lj_scene_rebuild_bvh: too many primitives for the 30-bit leaf code");
+        const int n = (int)n_prims;
+        lj_context *ctx = scene->ctx;
+        set_device(ctx);
+        hipStream_t s = ctx->stream;
+        // ---- device: the linear BVH, into the context's workspace (the scene is only read)
+        ensure(ctx->rebuild_ws, ljd::rebuild_carve(nullptr, n, s).bytes);
+        const ljd::RebuildWork w = ljd::rebuild_carve(ctx->rebuild_ws.p, n, s);
+        const auto t0 = std::chrono::steady_clock::now();
+        ljd::launch_rebuild_prim_boxes((const ljd::DPrim *)scene->leaf_prims.p, (int)F.leaf_prims.size(), (const ljd::DSphere *)scene->spheres.p, w, n, s);
+        std::vector<int> order;
+        const std::vector<lj::BinaryNode> tree = build_binary_tree(w, n, s, order);
+        const auto t1 = std::chrono::steady_clock::now();
+        // ---- host: the wide trees, the leaf order and the level tables; every refusal comes from here
+        lj::FlatScene R;
+        try { R = lj::rebuild_trees(F, tree, order, ljd::max_stack_depth()); }
+        catch (const LjError &e) { throw LjError(e.code, std::string("lj_scene_rebuild_bvh: ") + e.what()); }
+        // ---- nothing of the scene was written up to here
+        lj::commit_rebuild(F, std::move(R));
+        const auto t2 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipEventRecord(ctx->ev_begin, s));
+        install_trees(scene, s);
+        alloc_refit_tables(scene, s);
+        refit_launches(scene, s);
+        HIP_CHECK(hipEventRecord(ctx->ev_end, s));
+        read_back_nodes(scene, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        LjRebuildStats r = tree_stats(1);
+        r.build_ms = ms(t0, t1); r.emit_ms = ms(t1, t2); r.refit_ms = elapsed_ms(ctx->ev_begin, ctx->ev_end);
+        scene->rebuild_stats = r;
+        // LjStats of a rebuild: render_ms = device time (the build with its readback, the upload of the trees and the refit), generate_ms = host time
+        scene->stats = LjStats{}; scene->stats.render_ms = (float)(r.build_ms + r.refit_ms); scene->stats.generate_ms = (float)r.emit_ms;
+    });
+}
+
+int lj_get_rebuild_stats(const lj_scene *scene, LjRebuildStats *out) {
+    if (!scene || !out) { lj::set_last_error("lj_get_rebuild_stats: null argument"); return LJ_ERR_INVALID_ARG; }
+    *out = scene->rebuild_stats;
+    return LJ_OK;
+}
+
+int lj_bvh_build_query(lj_context *ctx, int64_t n, const float *boxes, int32_t *order_out, LjBinaryNode *nodes_out, int64_t capacity, int64_t *n_nodes) {
+    return lj::guard([&]() {
+        const std::string me("lj_bvh_build_query");
+        if (!ctx || !n_nodes) throw LjError(LJ_ERR_INVALID_ARG, me + ": null argument");
+        if (n < 0 || n * 8 >= (1ll << 30)) throw LjError(LJ_ERR_INVALID_ARG, me + ": n must be in [0, 2^27)");
+        if (n > 0 && (!boxes || !order_out)) throw LjError(LJ_ERR_INVALID_ARG, me + ": null array");
+        for (int64_t i = 0; i < n; i++) for (int k = 0; k < 3; k++) {
+            const float lo = boxes[6 * i + k], hi = boxes[6 * i + 3 + k];
+            if (!(lo <= hi) || !(std::fabs(lo) <= 3.402823466e38f) || !(std::fabs(hi) <= 3.402823466e38f)) throw LjError(LJ_ERR_INVALID_ARG, me + ": box " + std::to_string(i) + " is empty or not finite");
+        }
+        // ---- nothing was written up to here
+        *n_nodes = 0;
+        if (n == 0) return;
+        set_device(ctx);
+        hipStream_t s = ctx->stream;
+        ensure(ctx->rebuild_ws, ljd::rebuild_carve(nullptr, (int)n, s).bytes);
+        const ljd::RebuildWork w = ljd::rebuild_carve(ctx->rebuild_ws.p, (int)n, s);
+        HIP_CHECK(hipMemcpyAsync(w.boxes, boxes, (size_t)n * 24, hipMemcpyHostToDevice, s));
+        std::vector<int> order;
+        const std::vector<lj::BinaryNode> tree = build_binary_tree(w, (int)n, s, order);
+        *n_nodes = (int64_t)tree.size();
+        if (nodes_out && capacity < *n_nodes) throw LjError(LJ_ERR_INVALID_ARG, me + ": buffer too small");
+        for (int64_t i = 0; i < n; i++) order_out[i] = order[(size_t)i];
+        if (nodes_out) memcpy(nodes_out, tree.data(), tree.size() * sizeof(LjBinaryNode));
     });
 }
 

@@ -73,6 +73,14 @@ size_t refit_box_bytes();
 void launch_refit4(DNode4 *nodes, void *box4, const DPrim *leaf_prims, const DSphere *spheres, const int32_t *list, int n, hipStream_t s);
 void launch_refit8(void *nodes8, int stride, void *box8, const DPrim *leaf_prims, const DSphere *spheres, const int32_t *list, int n, hipStream_t s);
 void launch_refit_scan(DScanLeaf *leaves, const DPrim *leaf_prims, const DSphere *spheres, int n, hipStream_t s);
+// rebuild.hip: the linear BVH of lj_scene_rebuild_bvh (drebuild.h) over n primitives.  The pieces of one workspace: boxes (six floats per
+// primitive), order (sorted position -> primitive) and nodes (n - 1 records of rebuild_node_bytes(), boxes included) are what the host
+// reads back; the rest is scratch.  rebuild_carve(null, n, s).bytes is the size to allocate.
+struct RebuildWork { void *boxes, *bounds, *codes, *codes_sorted; int32_t *vals, *order; void *nodes; int32_t *parent; void *arrived, *sort_temp; size_t sort_temp_bytes, bytes; };
+RebuildWork rebuild_carve(void *workspace, int n, hipStream_t s);
+size_t rebuild_node_bytes();
+void launch_rebuild_prim_boxes(const DPrim *leaf_prims, int n_leaf_prims, const DSphere *spheres, const RebuildWork &w, int n, hipStream_t s);
+void launch_rebuild(const RebuildWork &w, int n, hipStream_t s);
 }
 
 using lj::LjError;
@@ -155,6 +163,7 @@ struct lj_context {
     // selection's flags and tile counts / offsets / total, the host variant's three outputs, and events around a round's merge and selection
     DevBuf ad_n, ad_mean, ad_m2, ad_rgb, ad_var, ad_list, ad_sel, ad_flags, ad_scan, ad_out;
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr, ev_a2 = nullptr;
+    DevBuf rebuild_ws;   // lj_scene_rebuild_bvh / lj_bvh_build_query: the workspace of rebuild.hip
 };
 
 struct lj_scene {
@@ -173,6 +182,7 @@ struct lj_scene {
     LjStats stats{};
     LjFeatureStats feature_stats{};   // of the last lj_render_features* call; zeros after any other render
     LjAdaptiveStats adaptive_stats{};   // of the last lj_render_adaptive* call; zeros after any other render
+    LjRebuildStats rebuild_stats{};   // of the last lj_scene_rebuild_bvh
 };
 
 inline void set_device(lj_context *ctx) { HIP_CHECK(hipSetDevice(ctx->device)); }

@@ -291,22 +291,159 @@ int grid_exponent(double extent) {
     return e;
 }
 
+namespace {
+
+ljd::DNode4 empty_node() {
+    const float inf = std::numeric_limits<float>::infinity();
+    ljd::DNode4 nd{};
+    for (int k = 0; k < 4; k++) { nd.lox[k] = nd.loy[k] = nd.loz[k] = inf; nd.hix[k] = nd.hiy[k] = nd.hiz[k] = -inf; nd.child[k] = 0; }
+    return nd;
+}
+ljd::DNode8 empty_node8() {
+    ljd::DNode8 nd{};
+    for (int k = 0; k < 3; k++) nd.e[k] = 1;
+    for (int k = 0; k < 8; k++) { nd.qlo_x[k] = nd.qlo_y[k] = nd.qlo_z[k] = 255; nd.qhi_x[k] = nd.qhi_y[k] = nd.qhi_z[k] = 0; }
+    return nd;
+}
+
+// The second half of build_bvh (flatten.h emit_wide) on the builder's own node type; `tmp` grows by the halves of leaves beyond four primitives.
+void emit_tmp(std::vector<TmpNode> &tmp, const std::vector<int> &order, int root, int max_depth4,
+              std::vector<ljd::DNode4> &nodes_out, std::vector<ljd::DNode8> &nodes8_out, std::vector<int> &leaf_order_out, int &depth_final, int &depth8_final) {
+    std::vector<ljd::DNode4> nodes; std::vector<ljd::DNode8> nodes8; std::vector<int> leaf_order; int depth_out = 0, depth8_out = 0;
+    auto finish = [&]() {
+        if (max_depth4 > 0 && depth_out > max_depth4)
+            throw LjError(LJ_ERR_UNSUPPORTED, "BVH depth " + std::to_string(depth_out) + " exceeds the traversal stack (" + std::to_string(max_depth4) + " levels)");
+        nodes_out = std::move(nodes); nodes8_out = std::move(nodes8); leaf_order_out = std::move(leaf_order); depth_final = depth_out; depth8_final = depth8_out;
+    };
+    // Beyond the depth cap the builder stops at leaves of up to 8 primitives (coincident primitives cannot be separated); the wide
+    // nodes want at most 4 per leaf, so such a leaf becomes an inner node over two leaves with its own box.
+    for (size_t id = 0; id < tmp.size(); id++) {
+        if (tmp[id].left >= 0 || tmp[id].count <= 4) continue;
+        TmpNode l = tmp[id], r = tmp[id];
+        l.count = 4; r.first = l.first + 4; r.count = tmp[id].count - 4; l.depth = r.depth = tmp[id].depth + 1;
+        tmp[id].left = (int)tmp.size(); tmp.push_back(l);
+        tmp[id].right = (int)tmp.size(); tmp.push_back(r);
+    }
+    auto is_leaf = [&](int id) { return tmp[id].left < 0; };
+
+    // ---- BVH8 first: it fixes the leaf order (the primitives of a wide node's leaf children are consecutive, in slot order)
+    std::vector<int> new_first(tmp.size(), -1);   // binary leaf id -> position of its first primitive in leaf_order
+    {
+        struct Wide8 { int kids[8]; int n; int depth; };
+        std::vector<int> queue{root}, qdepth{1};
+        const bool root_leaf = is_leaf(root);
+        const Collapse collapse8(tmp, 8, root);
+        for (size_t h = 0; h < queue.size(); h++) {
+            Wide8 w; w.depth = qdepth[h];
+            if (root_leaf) { w.kids[0] = root; w.n = 1; }
+            else {
+                collapse8.kids_of(queue[h], w.kids, w.n);
+            }
+            depth8_out = std::max(depth8_out, w.depth);
+            // grid: origin = lower corner of the union, one power-of-two step per axis
+            Box u; for (int k = 0; k < w.n; k++) u.grow(tmp[w.kids[k]].box);
+            ljd::DNode8 nd = empty_node8();
+            double step[3];
+            for (int a = 0; a < 3; a++) {
+                nd.p[a] = u.lo[a];
+                const int e = grid_exponent((double)u.hi[a] - (double)u.lo[a]);
+                nd.e[a] = (uint8_t)(e + 127); step[a] = std::ldexp(1.0, e);
+            }
+            // octant-ordered slots: child c goes to the free slot s that maximises (centre_c - centre_node) . corner_s, best pairs first
+            int slot_of[8]; bool slot_used[8] = {false}, kid_done[8] = {false};
+            double ctr[3]; for (int a = 0; a < 3; a++) ctr[a] = 0.5 * ((double)u.lo[a] + (double)u.hi[a]);
+            for (int round = 0; round < w.n; round++) {
+                double best = -std::numeric_limits<double>::infinity(); int bc = -1, bs = -1;
+                for (int c = 0; c < w.n; c++) if (!kid_done[c]) {
+                    const Box &cb = tmp[w.kids[c]].box;
+                    for (int s = 0; s < 8; s++) if (!slot_used[s]) {
+                        double v = 0;
+                        for (int a = 0; a < 3; a++) v += (0.5 * ((double)cb.lo[a] + (double)cb.hi[a]) - ctr[a]) * ((s >> a) & 1 ? 1.0 : -1.0);
+                        if (v > best) { best = v; bc = c; bs = s; }
+                    }
+                }
+                slot_of[bc] = bs; slot_used[bs] = true; kid_done[bc] = true;
+            }
+            int kid_at[8]; for (int s = 0; s < 8; s++) kid_at[s] = -1;
+            for (int c = 0; c < w.n; c++) kid_at[slot_of[c]] = w.kids[c];
+            nd.child_base = (uint32_t)queue.size(); nd.prim_base = (uint32_t)leaf_order.size();
+            for (int s = 0; s < 8; s++) {
+                const int id = kid_at[s];
+                if (id < 0) continue;
+                const Box &cb = tmp[id].box;
+                uint8_t *qlo[3] = {nd.qlo_x, nd.qlo_y, nd.qlo_z}, *qhi[3] = {nd.qhi_x, nd.qhi_y, nd.qhi_z};
+                for (int a = 0; a < 3; a++) {   // lower planes down, upper planes up, checked in exact arithmetic (q * step is exact in double)
+                    const double p = nd.p[a];
+                    long lo = (long)std::floor(((double)cb.lo[a] - p) / step[a]), hi = (long)std::ceil(((double)cb.hi[a] - p) / step[a]);
+                    lo = std::min(255l, std::max(0l, lo)); hi = std::min(255l, std::max(0l, hi));
+                    while (lo > 0 && p + lo * step[a] > (double)cb.lo[a]) lo--;
+                    while (hi < 255 && p + hi * step[a] < (double)cb.hi[a]) hi++;
+                    if (p + lo * step[a] > (double)cb.lo[a] || p + hi * step[a] < (double)cb.hi[a]) throw LjError(LJ_ERR_INTERNAL, "BVH8 grid does not contain a child box");
+                    qlo[a][s] = (uint8_t)lo; qhi[a][s] = (uint8_t)hi;
+                }
+                if (is_leaf(id)) {
+                    const TmpNode &t = tmp[id];
+                    const uint32_t off = (uint32_t)leaf_order.size() - nd.prim_base;
+                    nd.meta[s] = (uint8_t)(0x80u | ((uint32_t)(t.count - 1) << 5) | off);
+                    new_first[id] = (int)leaf_order.size();
+                    for (int i = 0; i < t.count; i++) leaf_order.push_back(order[t.first + i]);
+                } else {
+                    nd.imask |= (uint8_t)(1u << s);
+                    queue.push_back(id); qdepth.push_back(w.depth + 1);
+                }
+            }
+            nodes8.push_back(nd);
+            if (root_leaf) break;
+        }
+        if (nodes8.size() >= (1u << 24)) throw LjError(LJ_ERR_UNSUPPORTED, "too many BVH8 nodes for the 24-bit node index");
+    }
+
+    // ---- BVH4 over the same leaves
+    auto set_child = [&](ljd::DNode4 &nd, int k, int id, int code) {
+        const Box &bx = tmp[id].box;
+        nd.lox[k] = bx.lo[0]; nd.loy[k] = bx.lo[1]; nd.loz[k] = bx.lo[2];
+        nd.hix[k] = bx.hi[0]; nd.hiy[k] = bx.hi[1]; nd.hiz[k] = bx.hi[2];
+        nd.child[k] = code;
+    };
+    auto leaf_code = [&](int id) { return ~(new_first[id] * 8 + tmp[id].count - 1); };
+    if (is_leaf(root)) {
+        ljd::DNode4 nd = empty_node();
+        set_child(nd, 0, root, leaf_code(root));
+        nodes.push_back(nd); depth_out = 1;
+        finish();
+        return;
+    }
+    // collapse: a wide node starts from the two children of a binary node and opens its largest inner child until it
+    // has four; breadth-first numbering of the wide nodes
+    struct Wide { int kids[4]; int n; int depth; };
+    std::vector<Wide> wide;
+    std::vector<int> wide_of(tmp.size(), -1);  // binary node id -> wide node index (for the roots of wide nodes)
+    std::vector<int> queue{root};
+    wide_of[root] = 0;
+    std::vector<int> qdepth{1};
+    const Collapse collapse4(tmp, 4, root);
+    for (size_t h = 0; h < queue.size(); h++) {
+        Wide w; w.depth = qdepth[h];
+        collapse4.kids_of(queue[h], w.kids, w.n);
+        for (int k = 0; k < w.n; k++) if (!is_leaf(w.kids[k])) { wide_of[w.kids[k]] = (int)queue.size(); queue.push_back(w.kids[k]); qdepth.push_back(w.depth + 1); }
+        wide.push_back(w);
+        depth_out = std::max(depth_out, w.depth);
+    }
+    nodes.resize(wide.size());
+    for (size_t h = 0; h < wide.size(); h++) {
+        ljd::DNode4 nd = empty_node();
+        for (int k = 0; k < wide[h].n; k++) { const int id = wide[h].kids[k]; set_child(nd, k, id, is_leaf(id) ? leaf_code(id) : wide_of[id]); }
+        nodes[h] = nd;
+    }
+    finish();
+}
+
+} // namespace
+
 void build_bvh(const std::vector<BuildPrim> &prims, int max_leaf, int max_depth,
                std::vector<ljd::DNode4> &nodes, std::vector<ljd::DNode8> &nodes8, std::vector<int> &leaf_order, int &depth_out, int &depth8_out) {
     nodes.clear(); nodes8.clear(); leaf_order.clear(); depth_out = 0; depth8_out = 0;
     const int n = (int)prims.size();
-    const float inf = std::numeric_limits<float>::infinity();
-    auto empty_node = [&]() {
-        ljd::DNode4 nd{};
-        for (int k = 0; k < 4; k++) { nd.lox[k] = nd.loy[k] = nd.loz[k] = inf; nd.hix[k] = nd.hiy[k] = nd.hiz[k] = -inf; nd.child[k] = 0; }
-        return nd;
-    };
-    auto empty_node8 = [&]() {
-        ljd::DNode8 nd{};
-        for (int k = 0; k < 3; k++) nd.e[k] = 1;
-        for (int k = 0; k < 8; k++) { nd.qlo_x[k] = nd.qlo_y[k] = nd.qlo_z[k] = 255; nd.qhi_x[k] = nd.qhi_y[k] = nd.qhi_z[k] = 0; }
-        return nd;
-    };
     if (n == 0) { nodes.push_back(empty_node()); nodes8.push_back(empty_node8()); depth_out = 1; depth8_out = 1; return; }
     // Spatial splits for scenes beyond the tiny ones (those run the flat leaf scan of mega.hip, which indexes primitives with 16 bits
     // and wants no duplicates); at most twice as many references as primitives (sponza ends at 1.36x: -16 % node steps and -30 %
@@ -327,125 +464,53 @@ void build_bvh(const std::vector<BuildPrim> &prims, int max_leaf, int max_depth,
     b.tmp.reserve(2 * (size_t)n);
     const int root = b.build(refs, 0);
     if ((long long)n * 8 >= (1ll << 30)) throw LjError(LJ_ERR_UNSUPPORTED, "too many primitives for the 30-bit leaf code");
-    // Beyond the depth cap the builder stops at leaves of up to 8 primitives (coincident primitives cannot be separated); the wide
-    // nodes want at most 4 per leaf, so such a leaf becomes an inner node over two leaves with its own box.
-    for (size_t id = 0; id < b.tmp.size(); id++) {
-        if (b.tmp[id].left >= 0 || b.tmp[id].count <= 4) continue;
-        TmpNode l = b.tmp[id], r = b.tmp[id];
-        l.count = 4; r.first = l.first + 4; r.count = b.tmp[id].count - 4; l.depth = r.depth = b.tmp[id].depth + 1;
-        b.tmp[id].left = (int)b.tmp.size(); b.tmp.push_back(l);
-        b.tmp[id].right = (int)b.tmp.size(); b.tmp.push_back(r);
-    }
-    auto is_leaf = [&](int id) { return b.tmp[id].left < 0; };
+    emit_tmp(b.tmp, b.order, root, 0, nodes, nodes8, leaf_order, depth_out, depth8_out);
+}
 
-    // ---- BVH8 first: it fixes the leaf order (the primitives of a wide node's leaf children are consecutive, in slot order)
-    std::vector<int> new_first(b.tmp.size(), -1);   // binary leaf id -> position of its first primitive in leaf_order
-    {
-        struct Wide8 { int kids[8]; int n; int depth; };
-        std::vector<int> queue{root}, qdepth{1};
-        const bool root_leaf = is_leaf(root);
-        const Collapse collapse8(b.tmp, 8, root);
-        for (size_t h = 0; h < queue.size(); h++) {
-            Wide8 w; w.depth = qdepth[h];
-            if (root_leaf) { w.kids[0] = root; w.n = 1; }
-            else {
-                collapse8.kids_of(queue[h], w.kids, w.n);
-            }
-            depth8_out = std::max(depth8_out, w.depth);
-            // grid: origin = lower corner of the union, one power-of-two step per axis
-            Box u; for (int k = 0; k < w.n; k++) u.grow(b.tmp[w.kids[k]].box);
-            ljd::DNode8 nd = empty_node8();
-            double step[3];
-            for (int a = 0; a < 3; a++) {
-                nd.p[a] = u.lo[a];
-                const int e = grid_exponent((double)u.hi[a] - (double)u.lo[a]);
-                nd.e[a] = (uint8_t)(e + 127); step[a] = std::ldexp(1.0, e);
-            }
-            // octant-ordered slots: child c goes to the free slot s that maximises (centre_c - centre_node) . corner_s, best pairs first
-            int slot_of[8]; bool slot_used[8] = {false}, kid_done[8] = {false};
-            double ctr[3]; for (int a = 0; a < 3; a++) ctr[a] = 0.5 * ((double)u.lo[a] + (double)u.hi[a]);
-            for (int round = 0; round < w.n; round++) {
-                double best = -std::numeric_limits<double>::infinity(); int bc = -1, bs = -1;
-                for (int c = 0; c < w.n; c++) if (!kid_done[c]) {
-                    const Box &cb = b.tmp[w.kids[c]].box;
-                    for (int s = 0; s < 8; s++) if (!slot_used[s]) {
-                        double v = 0;
-                        for (int a = 0; a < 3; a++) v += (0.5 * ((double)cb.lo[a] + (double)cb.hi[a]) - ctr[a]) * ((s >> a) & 1 ? 1.0 : -1.0);
-                        if (v > best) { best = v; bc = c; bs = s; }
-                    }
-                }
-                slot_of[bc] = bs; slot_used[bs] = true; kid_done[bc] = true;
-            }
-            int kid_at[8]; for (int s = 0; s < 8; s++) kid_at[s] = -1;
-            for (int c = 0; c < w.n; c++) kid_at[slot_of[c]] = w.kids[c];
-            nd.child_base = (uint32_t)queue.size(); nd.prim_base = (uint32_t)leaf_order.size();
-            for (int s = 0; s < 8; s++) {
-                const int id = kid_at[s];
-                if (id < 0) continue;
-                const Box &cb = b.tmp[id].box;
-                uint8_t *qlo[3] = {nd.qlo_x, nd.qlo_y, nd.qlo_z}, *qhi[3] = {nd.qhi_x, nd.qhi_y, nd.qhi_z};
-                for (int a = 0; a < 3; a++) {   // lower planes down, upper planes up, checked in exact arithmetic (q * step is exact in double)
-                    const double p = nd.p[a];
-                    long lo = (long)std::floor(((double)cb.lo[a] - p) / step[a]), hi = (long)std::ceil(((double)cb.hi[a] - p) / step[a]);
-                    lo = std::min(255l, std::max(0l, lo)); hi = std::min(255l, std::max(0l, hi));
-                    while (lo > 0 && p + lo * step[a] > (double)cb.lo[a]) lo--;
-                    while (hi < 255 && p + hi * step[a] < (double)cb.hi[a]) hi++;
-                    if (p + lo * step[a] > (double)cb.lo[a] || p + hi * step[a] < (double)cb.hi[a]) throw LjError(LJ_ERR_INTERNAL, "BVH8 grid does not contain a child box");
-                    qlo[a][s] = (uint8_t)lo; qhi[a][s] = (uint8_t)hi;
-                }
-                if (is_leaf(id)) {
-                    const TmpNode &t = b.tmp[id];
-                    const uint32_t off = (uint32_t)leaf_order.size() - nd.prim_base;
-                    nd.meta[s] = (uint8_t)(0x80u | ((uint32_t)(t.count - 1) << 5) | off);
-                    new_first[id] = (int)leaf_order.size();
-                    for (int i = 0; i < t.count; i++) leaf_order.push_back(b.order[t.first + i]);
-                } else {
-                    nd.imask |= (uint8_t)(1u << s);
-                    queue.push_back(id); qdepth.push_back(w.depth + 1);
-                }
-            }
-            nodes8.push_back(nd);
-            if (root_leaf) break;
-        }
-        if (nodes8.size() >= (1u << 24)) throw LjError(LJ_ERR_UNSUPPORTED, "too many BVH8 nodes for the 24-bit node index");
+void emit_wide(const std::vector<BinaryNode> &tree, const std::vector<int> &order, int root, int max_depth4,
+               std::vector<ljd::DNode4> &nodes, std::vector<ljd::DNode8> &nodes8, std::vector<int> &leaf_order, int &depth_out, int &depth8_out) {
+    if (tree.empty() || root < 0 || root >= (int)tree.size()) throw LjError(LJ_ERR_INVALID_ARG, "emit_wide: no root");
+    if ((long long)order.size() * 8 >= (1ll << 30)) throw LjError(LJ_ERR_UNSUPPORTED, "too many primitives for the 30-bit leaf code");
+    std::vector<TmpNode> tmp(tree.size());
+    for (size_t i = 0; i < tree.size(); i++) {
+        const BinaryNode &t = tree[i];
+        const bool leaf = t.left < 0;
+        if (leaf ? (t.first < 0 || t.count < 1 || t.count > 8 || (size_t)t.first + (size_t)t.count > order.size()) : (t.left >= (int)tree.size() || t.right < 0 || t.right >= (int)tree.size()))
+            throw LjError(LJ_ERR_INVALID_ARG, "emit_wide: node " + std::to_string(i) + " points outside the tree");
+        for (int k = 0; k < 3; k++) { tmp[i].box.lo[k] = t.lo[k]; tmp[i].box.hi[k] = t.hi[k]; }
+        tmp[i].left = leaf ? -1 : t.left; tmp[i].right = leaf ? -1 : t.right; tmp[i].first = t.first; tmp[i].count = t.count;
     }
+    emit_tmp(tmp, order, root, max_depth4, nodes, nodes8, leaf_order, depth_out, depth8_out);
+}
 
-    // ---- BVH4 over the same leaves
-    auto set_child = [&](ljd::DNode4 &nd, int k, int id, int code) {
-        const Box &bx = b.tmp[id].box;
-        nd.lox[k] = bx.lo[0]; nd.loy[k] = bx.lo[1]; nd.loz[k] = bx.lo[2];
-        nd.hix[k] = bx.hi[0]; nd.hiy[k] = bx.hi[1]; nd.hiz[k] = bx.hi[2];
-        nd.child[k] = code;
+std::vector<BinaryNode> compact_radix_tree(const void *raw_bytes, const float *boxes, const int32_t *order, int64_t n) {
+    std::vector<BinaryNode> out;
+    if (n <= 0) return out;
+    const BinaryNode *raw = (const BinaryNode *)raw_bytes;   // (ljd::RebuildNode: the same 40 bytes, children coded as drebuild.h says)
+    auto single = [&](int32_t pos) {
+        BinaryNode b{};
+        for (int k = 0; k < 3; k++) { b.lo[k] = boxes[6 * (size_t)order[pos] + k]; b.hi[k] = boxes[6 * (size_t)order[pos] + 3 + k]; }
+        b.left = b.right = -1; b.first = pos; b.count = 1;
+        return b;
     };
-    auto leaf_code = [&](int id) { return ~(new_first[id] * 8 + b.tmp[id].count - 1); };
-    if (is_leaf(root)) {
-        ljd::DNode4 nd = empty_node();
-        set_child(nd, 0, root, leaf_code(root));
-        nodes.push_back(nd); depth_out = 1;
-        return;
+    if (n == 1) { out.push_back(single(0)); return out; }
+    std::vector<int32_t> source{0};   // per output node: the raw node it came from, or ~position of a single primitive
+    out.push_back(raw[0]);
+    for (size_t h = 0; h < out.size(); h++) {
+        if (source[h] < 0) continue;
+        BinaryNode &nd = out[h];
+        const int32_t kids[2] = {nd.left, nd.right};
+        if (nd.count <= 4) { nd.left = nd.right = -1; continue; }
+        if ((size_t)out.size() + 2 > 2 * (size_t)n) throw LjError(LJ_ERR_INTERNAL, "the device's radix tree is not a tree");
+        for (int c = 0; c < 2; c++) {
+            const int32_t k = kids[c];
+            if (k >= n - 1 || ~k >= n) throw LjError(LJ_ERR_INTERNAL, "the device's radix tree points outside itself");
+            (c == 0 ? out[h].left : out[h].right) = (int32_t)out.size();
+            source.push_back(k);
+            if (k < 0) out.push_back(single(~k)); else out.push_back(raw[k]);
+        }
     }
-    // collapse: a wide node starts from the two children of a binary node and opens its largest inner child until it
-    // has four; breadth-first numbering of the wide nodes
-    struct Wide { int kids[4]; int n; int depth; };
-    std::vector<Wide> wide;
-    std::vector<int> wide_of(b.tmp.size(), -1);  // binary node id -> wide node index (for the roots of wide nodes)
-    std::vector<int> queue{root};
-    wide_of[root] = 0;
-    std::vector<int> qdepth{1};
-    const Collapse collapse4(b.tmp, 4, root);
-    for (size_t h = 0; h < queue.size(); h++) {
-        Wide w; w.depth = qdepth[h];
-        collapse4.kids_of(queue[h], w.kids, w.n);
-        for (int k = 0; k < w.n; k++) if (!is_leaf(w.kids[k])) { wide_of[w.kids[k]] = (int)queue.size(); queue.push_back(w.kids[k]); qdepth.push_back(w.depth + 1); }
-        wide.push_back(w);
-        depth_out = std::max(depth_out, w.depth);
-    }
-    nodes.resize(wide.size());
-    for (size_t h = 0; h < wide.size(); h++) {
-        ljd::DNode4 nd = empty_node();
-        for (int k = 0; k < wide[h].n; k++) { const int id = wide[h].kids[k]; set_child(nd, k, id, is_leaf(id) ? leaf_code(id) : wide_of[id]); }
-        nodes[h] = nd;
-    }
+    return out;
 }
 
 } // namespace lj

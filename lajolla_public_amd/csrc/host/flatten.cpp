@@ -590,4 +590,36 @@ void commit_update(FlatScene &F, FlatScene &&U) {
     F.shadow_epsilon = U.shadow_epsilon;
 }
 
+FlatScene rebuild_trees(const FlatScene &prev, const std::vector<BinaryNode> &tree, const std::vector<int> &order, int max_depth4) {
+    const size_t n = prev.prims.size();
+    if (order.size() != n || prev.leaf_order.size() != prev.leaf_prims.size()) throw LjError(LJ_ERR_INTERNAL, "lj_scene_rebuild_bvh: the order does not cover the primitives");
+    FlatScene R;
+    std::vector<int> leaf_order;
+    emit_wide(tree, order, 0, max_depth4, R.nodes, R.nodes8, leaf_order, R.bvh_depth, R.bvh8_depth);
+    // the global primitives, recovered from the leaf-ordered ones (every one of them is in some leaf)
+    std::vector<int32_t> at(n, -1);
+    for (size_t i = 0; i < prev.leaf_order.size(); i++) {
+        const int32_t g = prev.leaf_order[i];
+        if (g < 0 || (size_t)g >= n) throw LjError(LJ_ERR_INTERNAL, "lj_scene_rebuild_bvh: leaf order outside the primitives");
+        at[g] = (int32_t)i;
+    }
+    if (leaf_order.size() != n) throw LjError(LJ_ERR_INTERNAL, "lj_scene_rebuild_bvh: the rebuilt leaves do not hold every primitive once");
+    std::vector<char> seen(n, 0);
+    R.leaf_order.resize(n); R.leaf_prims.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const int g = leaf_order[i];
+        if (g < 0 || (size_t)g >= n || seen[g] || at[g] < 0) throw LjError(LJ_ERR_INTERNAL, "lj_scene_rebuild_bvh: the rebuilt leaves do not hold every primitive once");
+        seen[g] = 1;
+        R.leaf_order[i] = g; R.leaf_prims[i] = prev.leaf_prims[(size_t)at[g]];
+    }
+    build_levels(R);
+    return R;
+}
+
+void commit_rebuild(FlatScene &F, FlatScene &&R) {
+    F.nodes = std::move(R.nodes); F.nodes8 = std::move(R.nodes8); F.leaf_order = std::move(R.leaf_order); F.leaf_prims = std::move(R.leaf_prims);
+    F.levels4 = std::move(R.levels4); F.level4_first = std::move(R.level4_first); F.levels8 = std::move(R.levels8); F.level8_first = std::move(R.level8_first);
+    F.bvh_depth = R.bvh_depth; F.bvh8_depth = R.bvh8_depth;
+}
+
 } // namespace lj

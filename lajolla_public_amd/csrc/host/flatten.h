@@ -85,4 +85,24 @@ struct BuildPrim { float lo[3], hi[3]; float v[3][3]; int tri; };
 void build_bvh(const std::vector<BuildPrim> &prims, int max_leaf, int max_depth,
                std::vector<ljd::DNode4> &nodes, std::vector<ljd::DNode8> &nodes8, std::vector<int> &leaf_order, int &depth_out, int &depth8_out);
 
+// bvh.cpp — the second half of build_bvh on a binary tree from anywhere (lj_scene_rebuild_bvh hands it the device's linear BVH).
+// One node of such a tree (the layout of LjBinaryNode): an inner node has left / right >= 0, a leaf has both < 0 and the primitives
+// order[first .. first + count).
+struct BinaryNode { float lo[3], hi[3]; int32_t left, right, first, count; };
+// Everything from the split of leaves beyond four primitives down: the collapse, BVH8 slots and quantisation, BVH4, both depths.
+// max_depth4 > 0: throws LjError(LJ_ERR_UNSUPPORTED) for a BVH4 deeper than that; throws it too at the 24-bit node and 30-bit leaf
+// index limits.  The outputs are written after the last check: a refused call leaves them as they were.
+void emit_wide(const std::vector<BinaryNode> &tree, const std::vector<int> &order, int root, int max_depth4,
+               std::vector<ljd::DNode4> &nodes, std::vector<ljd::DNode8> &nodes8, std::vector<int> &leaf_order, int &depth_out, int &depth8_out);
+// The reachable part of the device's radix tree (device/drebuild.h: raw[0] is the root of the n - 1 nodes over n >= 2 sorted primitives,
+// a node of at most four primitives is a leaf; n == 1: one leaf), compacted breadth-first from the root (root = 0).
+// raw: n - 1 records of 40 bytes (ljd::RebuildNode); boxes: float[6] per primitive; order: sorted position -> primitive.
+std::vector<BinaryNode> compact_radix_tree(const void *raw, const float *boxes, const int32_t *order, int64_t n);
+
+// lj_scene_rebuild_bvh, host part: from the compacted binary tree over the scene's global primitives (tree leaves index `order`, which
+// holds global primitive ids, each once), the trees, leaf order, leaf-ordered primitives (from prev's), level tables and depths of the
+// rebuilt scene — those fields only, nothing of `prev` is changed.  Throws what emit_wide throws.  commit_rebuild moves them into the scene.
+FlatScene rebuild_trees(const FlatScene &prev, const std::vector<BinaryNode> &tree, const std::vector<int> &order, int max_depth4);
+void commit_rebuild(FlatScene &scene, FlatScene &&rebuilt);
+
 } // namespace lj
