@@ -454,6 +454,72 @@ int lj_get_adaptive_stats(const lj_scene *scene, LjAdaptiveStats *out);
 int lj_adaptive_select_query(lj_context *ctx, int32_t width, int32_t height, const uint32_t *n, const float *mean, const float *m2,
                              const LjAdaptiveArgs *adaptive, const uint32_t *pixel_list, int64_t n_list, uint32_t *selected_out, int64_t *n_selected);
 
+/* ---- Radiance along given rays, irradiance at surface points: the integrator of lj_render started from a table of rays instead of a camera
+ * (lightmap texels, irradiance probes, a reflection gather, a validation ray through a medium).  DESIGN.md 3.11, csrc/device/dprobe.h.
+ *
+ * lj_radiance_rays.  Ray i, sample s of spp is one path whose first segment is (org_i, dir_i), traced exactly as the integrator traces a
+ * camera ray: tnear = 0 and tfar = inf for the path integrator and for volpath versions 1 and 2, tnear = LjSceneInfo.shadow_epsilon for the
+ * full volpath (its camera rays start there as well).  Origins are used as given: callers who start on a surface offset them themselves,
+ * by LjSceneInfo.shadow_epsilon along the normal as lj_irradiance does.  Directions must be unit vectors.
+ *   The path draws from pcg32 stream i * spp + s of args->seed, and THE FIRST TWO DRAWS OF THE STREAM ARE TAKEN AND DISCARDED: they are the
+ *   two a camera sample spends on its jitter (jy, jx).  From there the path is what path_tracing() / vol_path_tracing() make of a camera ray:
+ *   emission seen directly at the first hit is included; max_depth, rr_depth and the scene's volpath version apply as for lj_render.
+ *   Consequence: let ray p * k + s be camera sample (pixel p, sample s) of a k-spp render — origin the camera's, direction that of
+ *   lj_primary_ray_queries with the sample's jitter — and trace the table with spp = 1, the same seed and max_depth: the result is bit for
+ *   bit what lj_render_samples returns for that sample, whichever kernel plan rendered it.
+ *   path:    ray_spread seeds the RayDifferential spread of the first segment (texture footprints); medium_id is not used.
+ *   volpath: the path starts in medium_id with spread 0, as its camera samples do; ray_spread is not used.
+ *   radiance[i] is the float sum of ray i's spp samples in the order lj_render's resolve sums a pixel's, times 1 / spp; variance[i] the
+ *   squared standard error of that mean by the two-pass formula of lj_render_features (0 when spp == 1); samples the raw per-sample values.
+ *   Results are bit-identical from call to call and for any pool_paths / pass size, and prefix-stable: ray i's outputs depend only on
+ *   (rays[i], i, spp, seed, max_depth), so the first m rays of a call give what a call with only those m gives.
+ *   A tiny scene, whose renders run the fused persistent kernel, takes the wavefront kernels for these calls (same per-sample values).
+ *   What a ray costs against a pixel sample (one MI355X, device time, the camera's own 16 samples per pixel fed back as rays):
+ *   cbox 512 x 512: 1202 Msamples/s against lj_render's 3474 (2.9 times the time: the wavefront plan against the fused kernel);
+ *   disney_bsdf 683 x 512: 526 against 549 (1.04 times).  The blocking call adds the upload, the host-side check and the read-back of the table:
+ *   ~30 ns of wall time per ray.  lj_get_stats afterwards is what a render of n * spp samples leaves.
+ * args: spp (<= 0: the scene's samples per pixel), max_depth, seed, pool_paths and flags as for lj_render.
+ * LjRaysArgs: NULL, or a zero-initialised struct, means all defaults — a field is read only when its LJ_RAYS_HAS_* bit is set in `flags`, so
+ * that zeroed memory never means "medium 0".
+ * LJ_ERR_UNSUPPORTED: rng_mode LJ_RNG_TILE; a scene with one of the five auxiliary integrators.
+ * LJ_ERR_INVALID_ARG: NULL scene / table / buffers, or buffers with all three pointers NULL; n < 0 or n > 2^31 (a list entry is 32 bits wide,
+ *   as for a batch of cameras); spp > 2^20 (n * spp itself is not bounded: a call runs in passes of at most 2^27 samples, whose sample ids
+ *   are 32 bits wide, and streams are 64 bits wide); rank / world_size other than 0 / 0-or-1, or a non-zero crop; an unknown flag; a
+ *   medium_id that is neither LJ_RAYS_CAMERA_MEDIUM nor in [-1, n_media); a ray_spread that is not finite; a ray that is not finite, or
+ *   whose | |dir| - 1 | exceeds 1e-4 (a float-normalised direction is off by ~1e-7).  The message names the first offending index.
+ * Every check runs on the host before the first device write: a refused call writes nothing.  n == 0 returns LJ_OK and launches nothing.
+ * All three calls block, take host pointers and are ordered on the context's stream.
+ *
+ * lj_irradiance.  Probe i, sample s, stream i * spp + s; here the two leading draws are USED: u0 is the first, u1 the second.
+ *   dir = to_world(make_frame(normal), sample_cos_hemisphere(u0, u1)) — the device functions the Lambertian's sample_bsdf calls, composed
+ *   the way it composes them, so a probe's ray is what a Lambertian surface at that point would have sampled — and
+ *   org = position + shadow_epsilon * normal in float.  Everything after that is the rule above with that ray.
+ *   radiance[i] = pi_f * mean_i and variance[i] = pi_f * pi_f * var_i (pi_f = 3.14159274f), one float multiply each: the cosine-weighted
+ *   estimator of E = integral of L cos(theta) over the hemisphere.  samples are the raw L values.  Normals are validated like directions.
+ * lj_probe_ray_queries (a test hook) returns exactly the (org, dir) the kernel builds, rays_out[i * spp + s]: fed to lj_radiance_rays at
+ *   spp = 1 with the same seed they reproduce lj_irradiance's samples bit for bit. */
+typedef struct LjRadianceRay { float org[3]; float dir[3]; } LjRadianceRay;          /* 24 bytes */
+typedef struct LjProbe       { float position[3]; float normal[3]; } LjProbe;        /* 24 bytes */
+#define LJ_RAYS_CAMERA_MEDIUM INT32_MIN
+enum { LJ_RAYS_HAS_MEDIUM = 1, LJ_RAYS_HAS_SPREAD = 2 };
+typedef struct LjRaysArgs {            /* NULL or all zero: all defaults */
+    int32_t medium_id;                 /* read with LJ_RAYS_HAS_MEDIUM only.  volpath: the medium the origins lie in, -1: none;
+                                          LJ_RAYS_CAMERA_MEDIUM, and the default: the scene camera's */
+    float   ray_spread;                /* read with LJ_RAYS_HAS_SPREAD only.  path: spread of the first segment; < 0, and the default: the
+                                          scene camera's, 0.25 / max(width, height) */
+    uint32_t flags;                    /* LJ_RAYS_HAS_* */
+} LjRaysArgs;
+typedef struct LjRadianceBuffers {     /* any pointer may be NULL: not wanted; all three NULL: LJ_ERR_INVALID_ARG */
+    float *radiance;   /* [n][3]       mean over the spp samples (lj_irradiance: the irradiance) */
+    float *variance;   /* [n][3]       squared standard error of that mean; 0 when spp == 1 */
+    float *samples;    /* [n][spp][3]  per-sample radiance, the layout of lj_render_samples with the ray index for the pixel */
+} LjRadianceBuffers;
+int lj_radiance_rays(lj_scene *scene, const LjRenderArgs *args, const LjRaysArgs *rays_args, int64_t n, const LjRadianceRay *rays_host,
+                     const LjRadianceBuffers *out_host);
+int lj_irradiance(lj_scene *scene, const LjRenderArgs *args, const LjRaysArgs *rays_args, int64_t n, const LjProbe *probes_host,
+                  const LjRadianceBuffers *out_host);
+int lj_probe_ray_queries(lj_scene *scene, const LjRenderArgs *args, int64_t n, const LjProbe *probes_host, LjRadianceRay *rays_out_host);
+
 /* Per-sample radiance for the crop window: out[((y-y0)*(x1-x0) + (x-x0))*spp + s][3] — one path_tracing()
  * value (path_tracing.h:7-325) per entry, for path-by-path parity tests. */
 int lj_render_samples(lj_scene *scene, const LjRenderArgs *args, float *radiance_host);

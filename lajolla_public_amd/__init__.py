@@ -563,6 +563,67 @@ def render_samples(scene, crop, **kw):
     return out
 
 
+def make_rays_args(medium_id=None, ray_spread=None):
+    """LjRaysArgs, or None when both are left to their defaults (the scene camera's medium and spread)."""
+    if medium_id is None and ray_spread is None:
+        return None
+    a = _abi.LjRaysArgs()
+    if medium_id is not None:
+        a.medium_id, a.flags = int(medium_id), a.flags | _abi.LJ_RAYS_HAS_MEDIUM
+    if ray_spread is not None:
+        a.ray_spread, a.flags = float(ray_spread), a.flags | _abi.LJ_RAYS_HAS_SPREAD
+    return a
+
+
+def _ray_table(a, b, what):
+    a, b = np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError(f"{what}: the two arrays must hold as many vectors")
+    return np.ascontiguousarray(np.concatenate([a, b], axis=1))   # (n, 6): LjRadianceRay / LjProbe
+
+
+def _radiance_call(fn, scene, table, spp, variance, samples, medium_id, ray_spread, kw):
+    args = make_args(spp=spp, **kw)
+    k = args.spp if args.spp > 0 else scene.info.spp
+    n = table.shape[0]
+    out, bufs = {"radiance": np.empty((n, 3), np.float32)}, _abi.LjRadianceBuffers()
+    if variance:
+        out["variance"] = np.empty((n, 3), np.float32)
+    if samples:
+        out["samples"] = np.empty((n, max(k, 0), 3), np.float32)
+    for name, a in out.items():
+        setattr(bufs, name, a.ctypes.data)
+    ra = make_rays_args(medium_id, ray_spread)
+    _check(fn(scene._h, C.byref(args), C.byref(ra) if ra is not None else None, n, _vp(table), C.byref(bufs)))
+    return out
+
+
+def radiance_rays(scene, org, dir, spp=0, variance=False, samples=False, medium_id=None, ray_spread=None, **render_kw):
+    """Path-traced radiance along given rays (lj_radiance_rays): org, dir (n, 3), dir of unit length.  A dict: "radiance" (n, 3) float32, the
+    mean over spp samples per ray; with variance=True "variance" (n, 3), its squared standard error; with samples=True "samples" (n, spp, 3).
+    Ray i, sample s draws from pcg32 stream i * spp + s (its first two draws are discarded, as a camera sample spends them on its jitter).
+    medium_id (volpath): the medium the origins lie in, None: the camera's; ray_spread (path): spread of the first segment, None: the camera's.
+    **render_kw: max_depth, seed, pool_paths, flags as for render()."""
+    return _radiance_call(load_library().lj_radiance_rays, scene, _ray_table(org, dir, "radiance_rays"), spp, variance, samples, medium_id, ray_spread, render_kw)
+
+
+def irradiance(scene, positions, normals, spp=0, variance=False, samples=False, medium_id=None, ray_spread=None, **render_kw):
+    """Irradiance at surface points (lj_irradiance): positions, normals (n, 3), normals of unit length.  Per probe, spp cosine-distributed
+    directions about the normal from the point offset by the scene's shadow epsilon; "radiance" is pi times the mean of the radiance along
+    them, "variance" pi^2 times its squared standard error, "samples" the radiance values themselves.  Arguments as radiance_rays()."""
+    return _radiance_call(load_library().lj_irradiance, scene, _ray_table(positions, normals, "irradiance"), spp, variance, samples, medium_id, ray_spread, render_kw)
+
+
+def probe_rays(scene, positions, normals, spp, seed=0):
+    """The rays irradiance() traces (lj_probe_ray_queries, a test hook): (org, dir), each (n, spp, 3) float32."""
+    table = _ray_table(positions, normals, "probe_rays")
+    args = make_args(spp=spp, seed=seed)
+    k = args.spp if args.spp > 0 else scene.info.spp
+    out = np.empty((table.shape[0], max(k, 0), 6), np.float32)
+    _check(load_library().lj_probe_ray_queries(scene._h, C.byref(args), table.shape[0], _vp(table), _vp(out)))
+    return out[..., :3].copy(), out[..., 3:].copy()
+
+
 def _rays_array(org, dir, tnear, tfar):
     org = np.asarray(org, np.float32).reshape(-1, 3)
     n = org.shape[0]

@@ -158,6 +158,26 @@ class LjAdaptiveStats(C.Structure):
     _fields_ = [("rounds", C.c_uint64), ("samples", C.c_uint64), ("round_pixels", C.c_uint64 * 64), ("select_ms", C.c_double), ("merge_ms", C.c_double)]
 
 
+LJ_RAYS_CAMERA_MEDIUM = INT32_MIN
+LJ_RAYS_HAS_MEDIUM, LJ_RAYS_HAS_SPREAD = 1, 2
+
+
+class LjRadianceRay(C.Structure):
+    _fields_ = [("org", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+class LjProbe(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class LjRaysArgs(C.Structure):
+    _fields_ = [("medium_id", C.c_int32), ("ray_spread", C.c_float), ("flags", C.c_uint32)]
+
+
+class LjRadianceBuffers(C.Structure):
+    _fields_ = [("radiance", C.c_void_p), ("variance", C.c_void_p), ("samples", C.c_void_p)]
+
+
 class LjRebuildStats(C.Structure):
     _fields_ = [("rebuilt", C.c_uint64), ("n_prims", C.c_uint64), ("n_leaves", C.c_uint64), ("n_nodes4", C.c_uint64), ("n_nodes8", C.c_uint64),
                 ("depth4", C.c_int32), ("depth8", C.c_int32), ("build_ms", C.c_double), ("emit_ms", C.c_double), ("refit_ms", C.c_double)]
@@ -290,6 +310,9 @@ SYMBOLS = [
     ("lj_get_adaptive_stats", C.c_int, [C.c_void_p, C.POINTER(LjAdaptiveStats)]),
     ("lj_adaptive_select_query", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LjAdaptiveArgs), C.c_void_p, C.c_int64, C.c_void_p,
                                            C.POINTER(C.c_int64)]),
+    ("lj_radiance_rays", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.POINTER(LjRaysArgs), C.c_int64, C.c_void_p, C.POINTER(LjRadianceBuffers)]),
+    ("lj_irradiance", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.POINTER(LjRaysArgs), C.c_int64, C.c_void_p, C.POINTER(LjRadianceBuffers)]),
+    ("lj_probe_ray_queries", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_intersect", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_occluded", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("lj_get_stats", C.c_int, [C.c_void_p, C.POINTER(LjStats)]),

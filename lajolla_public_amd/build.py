@@ -26,7 +26,7 @@ ORACLE_LIB = os.path.join(ROOT, "oracle", "_build", "liblj_oracle_asan.so" if _S
 TWIN_LIB = os.path.join(ROOT, "tests", "twin", "_build", "libljtwin_asan.so" if _SAN else "libljtwin.so")
 
 HOST_SOURCES = ["host/api_host.cpp", "host/scene_xml.cpp", "host/mesh_io.cpp", "host/image_io.cpp", "host/jpeg_decode.cpp", "host/exr_decode.cpp", "host/png_decode.cpp", "host/tga_bmp_decode.cpp", "host/flatten.cpp", "host/bvh.cpp"]
-HIP_SOURCES = ["device/kernels.hip", "device/extend.hip", "device/extend8.hip", "device/volpath.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip", "device/adaptive.hip", "device/rebuild.hip"]
+HIP_SOURCES = ["device/kernels.hip", "device/shade_rays.hip", "device/volpath.hip", "device/extend.hip", "device/extend8.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip", "device/adaptive.hip", "device/rebuild.hip"]
 ARCH = "gfx950"
 
 
@@ -101,7 +101,9 @@ def build_product(verbose=True):
         # vol_cbox per-sample parity went from a median 2e-7 to 0.15 — and sponza's per-sample median crossed its 1e-4 bar: measured, dropped)
         cmd = [_hipcc(), "-std=c++17", "-O3", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
                "-fno-gpu-rdc", "-fno-slp-vectorize"] + os.environ.get("LJ_EXTRA_HIPCC_FLAGS", "").split() + ["-c", s, "-o", o]
-        if _stale(o, [s] + headers) or not _same_cmd(o, cmd):
+        # (shade_rays.hip is compiled from the templates of kernels.hip, which it includes)
+        included = [os.path.join(CSRC, "device/kernels.hip")] if src == "device/shade_rays.hip" else []
+        if _stale(o, [s] + included + headers) or not _same_cmd(o, cmd):
             jobs.append(cmd)
     if jobs:
         if verbose:
@@ -337,6 +339,24 @@ def build_twin_rebuild(verbose=True):
     return TWIN_REBUILD_LIB
 
 
+TWIN_RAYS_LIB = os.path.join(ROOT, "tests", "twin_rays", "_build", "libljtwinrays_asan.so" if _SAN else "libljtwinrays.so")
+
+
+def build_twin_rays(verbose=True):
+    """Host build of the ray source of the device headers (device/dprobe.h: lj_radiance_rays, lj_irradiance) for the CPU-side tests; the flags of build_twin."""
+    src = os.path.join(ROOT, "tests", "twin_rays", "twin_rays.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_RAYS_LIB), exist_ok=True)
+    deps = [src] + _headers() + [os.path.join(CSRC, s) for s in ("host/flatten.cpp", "host/bvh.cpp")]
+    if _stale(TWIN_RAYS_LIB, deps):
+        if verbose:
+            print("[build] compiling the host twin of the ray source (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2", "-ffp-contract=off"] + _SAN_FLAGS + _host_fma_flag() + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+              "-o", TWIN_RAYS_LIB, src, os.path.join(CSRC, "host/flatten.cpp"), os.path.join(CSRC, "host/bvh.cpp"), "-lpthread"])
+    return TWIN_RAYS_LIB
+
+
 def build_reference_subset():
     """oracle/_ref from the reference's own sources — only where /root/reference exists (this container)."""
     script = os.path.join(ROOT, "oracle", "ref_build.sh")
@@ -361,4 +381,5 @@ if __name__ == "__main__":
         build_twin_denoise()
         build_twin_adaptive()
         build_twin_rebuild()
+        build_twin_rays()
     print(LIB)

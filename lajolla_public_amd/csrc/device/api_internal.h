@@ -32,6 +32,8 @@ void launch_aux(const DScene &sc, const DPass &pass, uint32_t n_pixels, int inte
 void launch_volpath(const DScene &sc, const DPass &pass, uint32_t n_samples, uint32_t *counters, const ExtendConfig &cfg, int shade_variant, bool plain, int *spill, int grid, hipStream_t s);
 int volpath_blocks_per_cu(const DScene &sc);
 void launch_trace_rays(const DScene &sc, const void *rays, long long n, void *hits, unsigned char *occ, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
+// queries.hip: the first segments (six floats: org, dir) of the n_samples samples of a pass over a table of probes (lj_probe_ray_queries)
+void launch_probe_rays(const DScene &sc, const DPass &pass, uint32_t n_samples, float *rays_out, int n_cus, hipStream_t s);
 // features.hip: the guide buffers and the variance of a pass (lj_render_features; `want`: the FEAT_* bits of dtypes.h)
 int features_grid(uint64_t n_pixels, uint32_t spp, int n_cus);
 void launch_features(const DScene &sc, const DPass &pass, uint32_t n_pixels, uint32_t want, float *albedo, float *normal, float *depth, float *alpha, const ExtendConfig &cfg, int *spill, int grid, hipStream_t s);
@@ -147,6 +149,7 @@ struct lj_context {
     uint64_t pixel_list_key = 0;   // which pixel list `pixel_list` holds (RenderPlan::pixels_key), 0: none
     DevBuf tile_cursors, tile_list, tile_samples;   // the per-tile schedule: one cursor per tile (dtile.h), the tile ids, per-sample radiance
     DevBuf view_table;   // the camera table of a batch (lj_render_views): one DCamera per view, uploaded per call
+    DevBuf ray_table, ray_out;   // lj_radiance_rays / lj_irradiance: the table of rays or probes, uploaded per call, and the radiance and variance of its entries
     DevBuf mega_state;   // k_mega: [0] the grid-wide camera-sample counter (uint32), [8..] five 64-bit statistics
     ljd::DBlockState *blocks_host = nullptr;  // pinned, kMaxBlocks entries
     unsigned long long *stats_host = nullptr; // pinned, 8 entries: where a launch's statistics are read back (one wait per pass, no staged copy)
@@ -178,6 +181,7 @@ struct lj_scene {
     uint32_t feat_kinds = 0; bool feat_textured = false, feat_envmap = false, feat_sphere_lights = false;   // what the scene holds (picks scfg.variant)
     std::shared_ptr<const std::vector<uint32_t>> plan_pixels; uint64_t plan_pixels_key = 0;   // the last render plan's pixel list (make_plan)
     std::shared_ptr<const std::vector<uint32_t>> views_pixels; uint64_t views_pixels_key = 0;   // ... and the last batch plan's (make_views_plan)
+    std::shared_ptr<const std::vector<uint32_t>> rays_pixels; uint64_t rays_pixels_key = 0;     // ... and the last table's identity list (make_rays_plan)
     std::vector<int64_t> shape_first_gprim;   // global primitive id of each shape's first primitive (shape order, then triangle order)
     LjStats stats{};
     LjFeatureStats feature_stats{};   // of the last lj_render_features* call; zeros after any other render
@@ -206,6 +210,9 @@ struct RenderPlan {
     // a batch of cameras (lj_render_views): `pixels` lists e = v*w*h + y*w + x — the single-view list, in its order, once per view — and
     // views_dev is the batch's camera table on the device (0 / null: the scene's one camera)
     int n_views = 0; const ljd::DCamera *views_dev = nullptr;
+    // a table of rays or probes (lj_radiance_rays / lj_irradiance): `pixels` is the identity list over the table's entries, rays_dev the table
+    // on the device (six floats per entry), ray_kind the RAY_SOURCE_* of dtypes.h (none: cameras), ray_spread / ray_medium what the paths start with
+    const float *rays_dev = nullptr; uint32_t ray_kind = 0; float ray_spread = 0.0f; int ray_medium = -1;
     // a features request (lj_render_features): device frames of the plan's size, written at the plan's pixels after every pass's resolve;
     // want: the FEAT_* bits (dtypes.h) of the frames that are asked for, 0: none — the render is then exactly lj_render's
     struct Features { uint32_t want = 0; float *albedo = nullptr, *normal = nullptr, *depth = nullptr, *alpha = nullptr, *variance = nullptr; } feat;
@@ -213,5 +220,7 @@ struct RenderPlan {
 inline bool timing_requested(const LjRenderArgs *a) { return a && (a->flags & 1u); }   // (LjRenderArgs::flags bit 0: time every kernel)
 RenderPlan make_plan(lj_scene *sc, const LjRenderArgs *a);
 RenderPlan make_views_plan(lj_scene *sc, const LjRenderArgs *a, int n_views);
+RenderPlan make_rays_plan(lj_scene *sc, const LjRenderArgs *a, int64_t n);
 void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *samples_host, hipStream_t stream, bool timing);
+void run_probe_rays(lj_scene *sc, const RenderPlan &plan, float *rays_host, hipStream_t stream);   // the first segments of a probes plan, pass by pass: rays_host[list position * spp + s][6]
 int *ensure_spill(lj_context *ctx, int levels, uint32_t grid);

@@ -233,9 +233,20 @@ struct DPass {
     // table of the batch's cameras, by_height / view_pixels (= w*h) decode e (dshade.h view_decode).  Null (a value-initialised DPass):
     // one camera, DScene::cam, and a list entry is y*w + x
     const DCamera *views;
-    DFastDiv by_height;
+    // a table of rays or probes (lj_radiance_rays / lj_irradiance, dprobe.h; ray_kind != RAY_SOURCE_NONE): the first vertex of a sample comes
+    // from entry e of the table — six floats: org, dir of a ray, or position, normal of a probe — and not from a camera; a list entry is e, so
+    // the stream of a sample is e * spp + s as for a pixel.  spread: what the first segment starts with (path); medium: the medium the origins
+    // lie in (volpath).  Such a pass has no views, so the three values share the bytes of by_height and ray_kind takes the struct's padding:
+    // a DPass is the 96 bytes it was, and a kernel that knows no rays is compiled from the arguments it had
+    union {
+        DFastDiv by_height;
+        struct { const float *table; float spread; int32_t medium; } ray;
+    };
     uint32_t view_pixels;
+    uint32_t ray_kind;   // RAY_SOURCE_NONE (a value-initialised DPass): a camera pass
 };
+static_assert(sizeof(DPass) == 96, "DPass keeps its size: the ray source lives in bytes a camera pass leaves unused");
+enum : uint32_t { RAY_SOURCE_NONE = 0u, RAY_SOURCE_RAYS = 1u, RAY_SOURCE_PROBES = 2u };
 inline void set_pass_divisors(DPass &p, uint32_t spp, uint32_t width) { p.spp = spp; p.by_spp = make_fast_div(spp); p.by_width = make_fast_div(width); }
 inline void set_pass_views(DPass &p, const DCamera *views, uint32_t width, uint32_t height) { p.views = views; p.by_height = make_fast_div(height); p.view_pixels = width * height; }
 

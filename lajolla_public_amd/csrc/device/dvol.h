@@ -12,6 +12,7 @@
 //                   void tick(int slot);   (developer instrumentation of the device kernel: a no-op everywhere else)
 #pragma once
 #include "dshade.h"
+#include "dprobe.h"
 
 namespace ljd {
 
@@ -203,10 +204,10 @@ LJ_HD f3 vol_nee(const DScene &sc, Tracer &tr, VolRng &rng, f3 p, int current_me
 }
 
 // vol_path_tracing_1 (vol_path_tracing.h:6-41): absorption only — a directly visible emitter through the exterior medium of its surface
+// In two pieces, like version 2 below: the primary ray of a camera sample, and the estimate along a ray (org, dir) — which a ray of
+// lj_radiance_rays takes as well (dprobe.h)
 template <class Ft, class Tracer>
-LJ_HD f3 vol_path_sample_1(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, VolRng &rng) {
-    const float jy = vrnd(rng), jx = vrnd(rng);
-    const f3 org = ld3(cam.org), dir = camera_primary_dir(cam, x, y, jx, jy);
+LJ_HD f3 vol_path_estimate_1(const DScene &sc, Tracer &tr, f3 org, f3 dir) {
     float t, hu, hv; int gprim;
     if (!tr.closest(org, dir, 0.0f, INFINITY, t, hu, hv, gprim)) return mk3(0, 0, 0);   // (sample_primary's tnear: camera.cpp:46)
     const DVertex vertex = build_vertex(sc, org, dir, t, hu, hv, gprim, 0.0f);
@@ -219,18 +220,23 @@ LJ_HD f3 vol_path_sample_1(const DScene &sc, const DCamera &cam, Tracer &tr, int
     if (vertex.light_id >= 0) Le = light_emission<Ft>(sc, sc.lights[vertex.light_id], -dir, vertex.gn);
     return transmittance * Le;
 }
+template <class Ft, class Tracer>
+LJ_HD f3 vol_path_sample_1(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, VolRng &rng) {
+    const float jy = vrnd(rng), jx = vrnd(rng);
+    const f3 org = ld3(cam.org), dir = camera_primary_dir(cam, x, y, jx, jy);
+    return vol_path_estimate_1<Ft>(sc, tr, org, dir);
+}
 
 // vol_path_tracing_2 (vol_path_tracing.h:46-147): one monochromatic homogeneous medium, single scattering, free flight on the red channel
 // (oracle/lj_oracle.cpp vol_path_tracing_2 lists what is kept of the reference's reading of an empty optional)
+// (`medium`: the medium the ray starts in — the camera's for a camera sample)
 template <class Ft, class Tracer>
-LJ_HD f3 vol_path_sample_2(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, VolRng &rng) {
-    const float jy = vrnd(rng), jx = vrnd(rng);
-    const f3 org = ld3(cam.org), dir = camera_primary_dir(cam, x, y, jx, jy);
+LJ_HD f3 vol_path_estimate_2(const DScene &sc, Tracer &tr, f3 org, f3 dir, int medium, VolRng &rng) {
     float th, hu, hv; int gprim;
     const bool hit = tr.closest(org, dir, 0.0f, INFINITY, th, hu, hv, gprim);
     DVertex vertex;
     float t_hit = INFINITY;
-    int medium_id = sc.cam_medium;
+    int medium_id = medium;
     if (hit) { vertex = build_vertex(sc, org, dir, th, hu, hv, gprim, 0.0f); t_hit = length(vertex.position - org); medium_id = sc.shape_media[2 * sc.prims[gprim].shape_id + 1]; }
     if (medium_id < 0) return mk3(0, 0, 0);
     const DMedium &med = sc.media[medium_id];
@@ -267,6 +273,12 @@ LJ_HD f3 vol_path_sample_2(const DScene &sc, const DCamera &cam, Tracer &tr, int
     f3 Le = mk3(0, 0, 0);
     if (vertex.light_id >= 0) Le = light_emission<Ft>(sc, sc.lights[vertex.light_id], -dir, vertex.gn);
     return vdiv3(transmittance, transmittance) * Le;
+}
+template <class Ft, class Tracer>
+LJ_HD f3 vol_path_sample_2(const DScene &sc, const DCamera &cam, Tracer &tr, int x, int y, VolRng &rng) {
+    const float jy = vrnd(rng), jx = vrnd(rng);
+    const f3 org = ld3(cam.org), dir = camera_primary_dir(cam, x, y, jx, jy);
+    return vol_path_estimate_2<Ft>(sc, tr, org, dir, sc.cam_medium, rng);
 }
 
 // vol_path_tracing (vol_path_tracing.h:503-869); see oracle/lj_oracle.cpp for the list of reference quirks kept.  Versions 3, 4 and 5 of
@@ -308,6 +320,24 @@ LJ_HD bool vol_path_begin(const DScene &sc, const DCamera &cam, Tracer &tr, int 
     P.eta_scale = 1.0f;
     return true;
 }
+// the same for a sample whose first segment (org, dir) is given and starts in `medium` (a pass over rays or probes, dprobe.h);
+// `rng`: the sample's stream after its two leading draws, where a camera sample's is after its jitter
+template <class Ft, class Tracer>
+LJ_HD bool vol_path_begin_ray(const DScene &sc, Tracer &tr, f3 org, f3 dir, int medium, VolRng rng, VolPath &P, f3 &result) {
+    P.rng = rng;
+    P.bounce_iterations = 0; P.guard = 0;
+    if (sc.vol_path_version == 1) { result = vol_path_estimate_1<Ft>(sc, tr, org, dir); return false; }
+    if (sc.vol_path_version == 2) { result = vol_path_estimate_2<Ft>(sc, tr, org, dir, medium, P.rng); return false; }
+    P.org = org; P.dir = dir;
+    P.spread = 0.0f;
+    P.current_medium = medium;
+    P.throughput = mk3(1, 1, 1); P.radiance = mk3(0, 0, 0);
+    P.bounces = 0;
+    P.dir_pdf = 0.0f; P.nee_p_cache = mk3(0, 0, 0);
+    P.multi_trans_pdf = mk3(1, 1, 1);
+    P.eta_scale = 1.0f;
+    return true;
+}
 template <class Ft, class Tracer>
 LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, VolRng rng, VolPath &P, f3 &result) { return vol_path_begin<Ft>(sc, sc.cam, tr, x, y, rng, P, result); }
 // the per-(pixel, sample) schedule: a fresh stream per sample
@@ -321,13 +351,20 @@ LJ_HD bool vol_path_begin(const DScene &sc, Tracer &tr, int x, int y, uint64_t s
     return vol_path_begin<Ft>(sc, sc.cam, tr, x, y, stream, seed, P, result);
 }
 // camera sample `sample` of a pass (k_volpath and its host twin): pixel, stream and — for a batch of cameras — the view from the list entry
-template <class Ft, bool VIEWS, class Tracer>
+// RAYS: the pass is a table of rays or probes (DPass::ray_kind, dprobe.h) and `sample` starts from its entry.  A compile-time switch like
+// VIEWS: tested at run time it moved the spilled registers of the single-camera instantiations of k_volpath
+template <class Ft, bool VIEWS, bool RAYS = false, class Tracer>
 LJ_HD bool vol_path_begin_sample(const DScene &sc, const DPass &pass, Tracer &tr, uint32_t sample, VolPath &P, f3 &result) {
     const uint32_t p = fast_div(sample, pass.by_spp), k = sample - p * pass.spp;
     const uint32_t pixel = pass.pixel_list[p];
     if constexpr (VIEWS) {
         const ViewPixel vp = view_decode(pass, pixel);
         return with_view_camera(pass, vp.view, [&](const DCamera &cam) { return vol_path_begin<Ft>(sc, cam, tr, vp.x, vp.y, (uint64_t)vp.pixel * pass.spp + k, pass.seed, P, result); });
+    }
+    else if constexpr (RAYS) {
+        VolRng rng;
+        const RayStart r = ray_source_sample(sc, pass, sample, rng.state, rng.inc);
+        return vol_path_begin_ray<Ft>(sc, tr, r.org, r.dir, pass.ray.medium, rng, P, result);
     }
     else return vol_path_begin<Ft>(sc, tr, (int)(pixel - fast_div(pixel, pass.by_width) * (uint32_t)sc.cam.width), (int)fast_div(pixel, pass.by_width), (uint64_t)pixel * pass.spp + k, pass.seed, P, result);
 }

@@ -16,6 +16,7 @@
 #include "dtrace.h"
 #include "dconfig.h"
 #include "dtrav.h"
+#include "dprobe.h"
 
 namespace ljd {
 
@@ -245,7 +246,10 @@ template <> struct ShadeOccupancy<FeatLambert> { static constexpr int waves = LJ
 template <> struct ShadeOccupancy<FeatLambertTex> { static constexpr int waves = LJ_SHADE_OCC_LARGE; };
 template <> struct ShadeOccupancy<FeatDisney> { static constexpr int waves = LJ_SHADE_OCC_LARGE; };
 
-template <class Ft, int STAGE, bool VIEWS>
+// RAYS: the pass is a table of rays or probes (DPass::ray_kind, dprobe.h): the refill loop starts paths from the table's entries instead of
+// camera samples.  A compile-time switch like VIEWS, and for its reason: tested at run time it moved the spilled registers of every
+// single-camera instantiation.  The RAYS instantiations are compiled in a translation unit of their own, shade_rays.hip.
+template <class Ft, int STAGE, bool VIEWS, bool RAYS = false>
 __global__ void __launch_bounds__(kBlock, ShadeOccupancy<Ft>::waves) k_shade(DScene sc, DPass pass, DQueue q, DQueue qo, ShadeSortBuf sb, DBlockState *blocks, uint32_t seg, ShadeStage stg, uint32_t *work, uint32_t *chunk_list, uint32_t parity, uint32_t extend_waves) {
     __shared__ uint32_t s_list_base;
     if (blockIdx.x == 0 && threadIdx.x == 0) work[0] = extend_waves;   // the extend launch that follows draws list entries beyond its own waves from it
@@ -268,7 +272,8 @@ __global__ void __launch_bounds__(kBlock, ShadeOccupancy<Ft>::waves) k_shade(DSc
     const uint32_t n_new = left < room ? left : room;
     for (uint32_t g = threadIdx.x; g < n_new; g += kBlock) {
         PathState ps;
-        generate_path<VIEWS>(sc, pass, next_sample + g, ps);
+        if constexpr (RAYS) generate_ray_path(sc, pass, next_sample + g, ps);
+        else generate_path<VIEWS>(sc, pass, next_sample + g, ps);
         q_store(qo, base + out + g, ps);
     }
     const uint32_t b = wave_sum(cnt.bounces), cl = wave_sum(cnt.closest), sh = wave_sum(cnt.shadow), dn = wave_sum(cnt.done);
@@ -353,6 +358,30 @@ __global__ void __launch_bounds__(kBlock, 2) k_tail(DScene sc, DPass pass, DQueu
     }
 }
 
+// shade_rays.hip: launch_shade for a pass over a table of rays or probes — the RAYS instantiations of k_shade
+void launch_shade_rays(const DScene &sc, const DPass &pass, const DQueue &q, const DQueue &qo, uint32_t *sort_perm, uint8_t *sort_keys, DBlockState *blocks, uint32_t n_blocks, uint32_t seg, const ShadeConfig &cfg, uint32_t *work, uint32_t *chunk_list, uint32_t parity, uint32_t extend_waves, hipStream_t s);
+
+// launch_shade's choice of instantiation for one kind of pass: feature set and staging from the scene's ShadeConfig
+template <bool VIEWS, bool RAYS>
+static void launch_shade_kind(const DScene &sc, const DPass &pass, const DQueue &q, const DQueue &qo, uint32_t *sort_perm, uint8_t *sort_keys, DBlockState *blocks, uint32_t n_blocks, uint32_t seg, const ShadeConfig &cfg, uint32_t *work, uint32_t *chunk_list, uint32_t parity, uint32_t extend_waves, hipStream_t s) {
+    ShadeSortBuf sb; sb.perm = sort_perm; sb.keys = sort_keys;
+    sb.octant_bin = (getenv("LJ_TUNE_OCTANT_BIN") && atoi(getenv("LJ_TUNE_OCTANT_BIN")) != 0) ? 1u : 0u;
+    const ShadeStage st = make_shade_stage(cfg);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kBlock), cfg.smem, s, sc, pass, q, qo, sb, blocks, seg, st, work, chunk_list, parity, extend_waves); };
+    // (a scene whose tables are not staged at all runs the all-features instantiation: lj_scene_upload picks it)
+    const int stage = cfg.smem == 0 ? 0 : (cfg.stage_prims ? 2 : 1);
+    if (stage == 0) { launch(k_shade<FeatAll, 0, VIEWS, RAYS>); return; }
+    with_shade_variant(cfg.variant, [&](auto ft) {
+        using Ft = decltype(ft);
+        if (stage == 2) launch(k_shade<Ft, 2, VIEWS, RAYS>); else launch(k_shade<Ft, 1, VIEWS, RAYS>);
+    });
+}
+
+#ifdef LJ_SHADE_RAYS_UNIT   // shade_rays.hip: the templates above, and this launcher alone
+void launch_shade_rays(const DScene &sc, const DPass &pass, const DQueue &q, const DQueue &qo, uint32_t *sort_perm, uint8_t *sort_keys, DBlockState *blocks, uint32_t n_blocks, uint32_t seg, const ShadeConfig &cfg, uint32_t *work, uint32_t *chunk_list, uint32_t parity, uint32_t extend_waves, hipStream_t s) {
+    launch_shade_kind<false, true>(sc, pass, q, qo, sort_perm, sort_keys, blocks, n_blocks, seg, cfg, work, chunk_list, parity, extend_waves, s);
+}
+#else
 // ---------------------------------------------------------------- resolve: radiance / spp, deterministic
 // One wave per pixel; lanes stride over the pixel's samples, then a fixed xor-butterfly combines the 64 partials.
 __global__ void __launch_bounds__(kBlock) k_resolve(DPass pass, uint32_t n_pixels, float *rgb) {
@@ -409,19 +438,10 @@ bool shade_sorts_segments(const ShadeConfig &cfg) {   // feature sets whose k_sh
     return sorted;
 }
 void launch_shade(const DScene &sc, const DPass &pass, const DQueue &q, const DQueue &qo, uint32_t *sort_perm, uint8_t *sort_keys, DBlockState *blocks, uint32_t n_blocks, uint32_t seg, const ShadeConfig &cfg, uint32_t *work, uint32_t *chunk_list, uint32_t parity, uint32_t extend_waves, hipStream_t s) {
-    ShadeSortBuf sb; sb.perm = sort_perm; sb.keys = sort_keys;
-    sb.octant_bin = (getenv("LJ_TUNE_OCTANT_BIN") && atoi(getenv("LJ_TUNE_OCTANT_BIN")) != 0) ? 1u : 0u;
-    const ShadeStage st = make_shade_stage(cfg);
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kBlock), cfg.smem, s, sc, pass, q, qo, sb, blocks, seg, st, work, chunk_list, parity, extend_waves); };
-    // (a scene whose tables are not staged at all runs the all-features instantiation: lj_scene_upload picks it)
-    const int stage = cfg.smem == 0 ? 0 : (cfg.stage_prims ? 2 : 1);
-    // (a batch of cameras, DPass::views, runs the VIEWS instantiations: dshade.h)
-    if (stage == 0) { if (pass.views) launch(k_shade<FeatAll, 0, true>); else launch(k_shade<FeatAll, 0, false>); return; }
-    with_shade_variant(cfg.variant, [&](auto ft) {
-        using Ft = decltype(ft);
-        if (pass.views) { if (stage == 2) launch(k_shade<Ft, 2, true>); else launch(k_shade<Ft, 1, true>); }
-        else if (stage == 2) launch(k_shade<Ft, 2, false>); else launch(k_shade<Ft, 1, false>);
-    });
+    // (a table of rays, DPass::ray_kind, runs the RAYS instantiations of shade_rays.hip; a batch of cameras, DPass::views, the VIEWS ones: dshade.h)
+    if (pass.ray_kind != RAY_SOURCE_NONE) launch_shade_rays(sc, pass, q, qo, sort_perm, sort_keys, blocks, n_blocks, seg, cfg, work, chunk_list, parity, extend_waves, s);
+    else if (pass.views) launch_shade_kind<true, false>(sc, pass, q, qo, sort_perm, sort_keys, blocks, n_blocks, seg, cfg, work, chunk_list, parity, extend_waves, s);
+    else launch_shade_kind<false, false>(sc, pass, q, qo, sort_perm, sort_keys, blocks, n_blocks, seg, cfg, work, chunk_list, parity, extend_waves, s);
 }
 // LDS the fused tail needs: the extend image followed by the shade tables; 0 when that does not fit one workgroup's share
 size_t tail_smem(const ExtendConfig &ecfg, const ShadeConfig &scfg) {
@@ -440,5 +460,6 @@ void launch_resolve(const DPass &pass, uint32_t n_pixels, float *rgb, hipStream_
     const uint32_t grid = (n_pixels + waves_per_block - 1) / waves_per_block;
     if (grid) hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(kBlock), 0, s, pass, n_pixels, rgb);
 }
+#endif   // LJ_SHADE_RAYS_UNIT
 
 } // namespace ljd

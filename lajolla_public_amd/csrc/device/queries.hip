@@ -159,7 +159,24 @@ __global__ void __launch_bounds__(kQBlock) k_medium_queries(DScene sc, const LjM
     }
 }
 
+// the first segments of a pass over a table of probes (lj_probe_ray_queries): out[i] = (org, dir) of sample i of the pass, by the function
+// the path kernels start such a sample with (dprobe.h)
+__global__ void __launch_bounds__(kQBlock) k_probe_rays(DScene sc, DPass pass, uint32_t n_samples, float *out) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kQBlock + threadIdx.x; i < n_samples; i += (unsigned long long)gridDim.x * kQBlock) {
+        uint64_t rng, inc;
+        const RayStart r = ray_source_sample(sc, pass, (uint32_t)i, rng, inc);
+        st3(out + 6ull * i, r.org); st3(out + 6ull * i + 3, r.dir);
+    }
+}
+
 } // namespace
+
+void launch_probe_rays(const DScene &sc, const DPass &pass, uint32_t n_samples, float *rays_out, int n_cus, hipStream_t s) {
+    if (!n_samples) return;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)n_samples + kQBlock - 1) / kQBlock, (int64_t)n_cus * 8));
+    hipLaunchKernelGGL(k_probe_rays, dim3(grid), dim3(kQBlock), 0, s, sc, pass, n_samples, rays_out);
+}
+
 } // namespace ljd
 
 namespace {

@@ -55,6 +55,9 @@ ljd::DPass make_pass(const lj_scene *sc, const RenderPlan &plan, uint64_t p0, ui
     pass.pixel_list = (const uint32_t *)sc->ctx->pixel_list.p + p0; pass.n_pixels = (uint32_t)np; ljd::set_pass_divisors(pass, (uint32_t)plan.spp, (uint32_t)sc->flat.cam.width);
     pass.seed = plan.seed; pass.sample_rgb = (float *)sc->ctx->sample_rgb.p;
     if (plan.n_views > 0) ljd::set_pass_views(pass, plan.views_dev, (uint32_t)sc->flat.cam.width, (uint32_t)sc->flat.cam.height);
+    if (plan.ray_kind != ljd::RAY_SOURCE_NONE) {   // (never with views: the ray source shares by_height's bytes, dtypes.h)
+        pass.ray.table = plan.rays_dev; pass.ray_kind = plan.ray_kind; pass.ray.spread = plan.ray_spread; pass.ray.medium = plan.ray_medium;
+    }
     return pass;
 }
 
@@ -63,6 +66,13 @@ struct Pass { uint64_t p0, np, total; ljd::DPass d; };   // the pixels [p0, p0 +
 Pass pass_at(const lj_scene *sc, const RenderPlan &plan, uint64_t p0, uint64_t pix_per_pass) {
     const uint64_t np = std::min<uint64_t>(pix_per_pass, plan.pixels->size() - p0);
     return Pass{p0, np, np * (uint64_t)plan.spp, make_pass(sc, plan, p0, np)};
+}
+
+// list entries per pass: the per-sample radiance buffer stays <= ~1.5 GiB and sample ids stay in 32 bits
+// (LJ_TUNE_PASS_SAMPLES, a developer knob: small passes, so that a test can put a pass boundary anywhere — inside a view of a batch, say — at a small size)
+uint64_t pixels_per_pass(const RenderPlan &plan) {
+    const uint64_t max_samples_pass = (uint64_t)std::min(1 << 27, std::max(64, env_int("LJ_TUNE_PASS_SAMPLES", 1 << 27)));
+    return std::min<uint64_t>(std::max<uint64_t>(1, max_samples_pass / (uint64_t)plan.spp), plan.pixels->size());
 }
 
 // room for the per-sample radiance of the largest pass
@@ -511,9 +521,8 @@ int *ensure_spill(lj_context *ctx, int levels, uint32_t grid) {
     return (int *)ctx->spill.p;
 }
 
-RenderPlan make_plan(lj_scene *sc, const LjRenderArgs *a) {
-    RenderPlan p;
-    const int w = sc->flat.cam.width, h = sc->flat.cam.height;
+// what a plan takes from the arguments whatever it renders: samples, seed, depth, pool
+static void plan_basics(const lj_scene *sc, const LjRenderArgs *a, RenderPlan &p) {
     p.spp = (a && a->spp > 0) ? a->spp : sc->flat.spp;
     if (p.spp <= 0) throw LjError(LJ_ERR_INVALID_ARG, "samples per pixel must be positive");
     p.seed = (a && a->seed) ? a->seed : 0x853c49e6748fea9bULL;
@@ -523,6 +532,12 @@ RenderPlan make_plan(lj_scene *sc, const LjRenderArgs *a) {
     // (tools/pool_big.sh, sponza 1024 spp: 2^25 828 ms, 2^26 811, 2^27 794, 2^28 793; disney_bsdf 256 spp: 97.3 / 93.4 / 91.8 / 91.5)
     p.pool = (a && a->pool_paths) ? a->pool_paths : (1u << 27);
     p.pool = std::max<uint32_t>(p.pool, 4096);
+}
+
+RenderPlan make_plan(lj_scene *sc, const LjRenderArgs *a) {
+    RenderPlan p;
+    const int w = sc->flat.cam.width, h = sc->flat.cam.height;
+    plan_basics(sc, a, p);
     p.rng_mode = a ? a->rng_mode : LJ_RNG_SAMPLE;
     if (p.rng_mode != LJ_RNG_SAMPLE && p.rng_mode != LJ_RNG_TILE) throw LjError(LJ_ERR_UNSUPPORTED, "rng_mode must be LJ_RNG_SAMPLE or LJ_RNG_TILE");
     int rank = a ? a->rank : 0, world = (a && a->world_size > 0) ? a->world_size : 1;
@@ -577,6 +592,22 @@ RenderPlan make_views_plan(lj_scene *sc, const LjRenderArgs *a, int n_views) {
     return p;
 }
 
+// The plan of a table of n rays or probes (lj_radiance_rays / lj_irradiance, dprobe.h): the identity list — entry i is ray i, so that a sample's
+// stream is i * spp + s — no tiles, no share, no crop, no views.  The caller (who has checked the arguments) sets the table and the ray source.
+RenderPlan make_rays_plan(lj_scene *sc, const LjRenderArgs *a, int64_t n) {
+    RenderPlan p;
+    plan_basics(sc, a, p);
+    p.rng_mode = LJ_RNG_SAMPLE;
+    p.rank = 0; p.world = 1; p.cx0 = 0; p.cy0 = 0; p.cx1 = sc->flat.cam.width; p.cy1 = sc->flat.cam.height;
+    uint64_t key = (0x7261797300000000ull ^ (uint64_t)n) * 1099511628211ull; key ^= (uint64_t)(uintptr_t)sc; key |= 1ull;
+    if (sc->rays_pixels && sc->rays_pixels_key == key) { p.pixels = sc->rays_pixels; p.pixels_key = key; return p; }
+    auto list = std::make_shared<std::vector<uint32_t>>((size_t)n);
+    for (int64_t i = 0; i < n; i++) (*list)[(size_t)i] = (uint32_t)i;
+    p.pixels = list; p.pixels_key = key;
+    sc->rays_pixels = list; sc->rays_pixels_key = key;
+    return p;
+}
+
 // Renders plan.pixels; if rgb_dev != null writes radiance/spp there (other pixels untouched), if samples_host != null
 // the per-sample radiance of every pass is copied to host memory in pixel-list order.  One driver per kernel plan, picked in this order.
 void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *samples_host, hipStream_t stream, bool timing) {
@@ -589,13 +620,29 @@ void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *sam
     ljd::DScene ds = sc->dscene;   // the scene as the plan's kernels see it
     ds.max_depth = plan.max_depth;
     if (plan.rng_mode == LJ_RNG_TILE) return render_tiles(sc, ds, plan, rgb_dev, samples_host, stream);   // (the auxiliary integrators draw nothing: as above)
-    // pass size: keep the per-sample radiance buffer <= ~1.5 GiB and sample ids in 32 bits
-    // (LJ_TUNE_PASS_SAMPLES, a developer knob: small passes, so that a test can put a pass boundary anywhere — inside a view of a batch, say — at a small size)
-    const uint64_t max_samples_pass = (uint64_t)std::min(1 << 27, std::max(64, env_int("LJ_TUNE_PASS_SAMPLES", 1 << 27)));
-    const uint64_t pix_per_pass = std::min<uint64_t>(std::max<uint64_t>(1, max_samples_pass / (uint64_t)plan.spp), plan.pixels->size());
+    const uint64_t pix_per_pass = pixels_per_pass(plan);
     // a features request: room in the overflow stacks for the guide-buffer launch of the largest pass, before a driver takes its part of them
     if (plan.feat.want & ljd::FEAT_FIRST_HIT) ensure_spill(sc->ctx, sc->ecfg.spill_levels, (uint32_t)ljd::features_grid(pix_per_pass, (uint32_t)plan.spp, sc->ctx->n_cus));
     if (sc->flat.integrator == LJ_INTEGRATOR_VOLPATH) return render_volpath(sc, ds, plan, pix_per_pass, rgb_dev, samples_host, stream);
-    if (ljd::mega_smem(sc->dscene, sc->scfg) > 0 && mega_enabled()) return render_mega(sc, ds, plan, pix_per_pass, rgb_dev, samples_host, stream, timing);
+    // (a table of rays never runs k_mega: its first vertices are made in the refill loop of k_shade and in k_volpath alone)
+    if (plan.ray_kind == ljd::RAY_SOURCE_NONE && ljd::mega_smem(sc->dscene, sc->scfg) > 0 && mega_enabled()) return render_mega(sc, ds, plan, pix_per_pass, rgb_dev, samples_host, stream, timing);
     render_wavefront(sc, ds, plan, pix_per_pass, rgb_dev, samples_host, stream, timing);
+}
+
+// lj_probe_ray_queries: the passes of run_render over a probes plan, each answered by k_probe_rays instead of a path kernel — the same list,
+// the same pass arithmetic, the same DPass, so that a sample's ray here is the ray its path starts with there.
+void run_probe_rays(lj_scene *sc, const RenderPlan &plan, float *rays_host, hipStream_t stream) {
+    set_device(sc->ctx);
+    if (plan.pixels->empty()) return;
+    lj_context *ctx = sc->ctx;
+    const uint64_t pix_per_pass = pixels_per_pass(plan);
+    ensure(ctx->ray_out, pix_per_pass * (uint64_t)plan.spp * 24);
+    upload_pixel_list(ctx, plan, stream);
+    for (uint64_t p0 = 0; p0 < plan.pixels->size(); p0 += pix_per_pass) {
+        const Pass P = pass_at(sc, plan, p0, pix_per_pass);
+        ljd::launch_probe_rays(sc->dscene, P.d, (uint32_t)P.total, (float *)ctx->ray_out.p, ctx->n_cus, stream);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(rays_host + P.p0 * (uint64_t)plan.spp * 6, ctx->ray_out.p, P.total * 24, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
 }

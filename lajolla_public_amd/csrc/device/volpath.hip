@@ -15,7 +15,7 @@ namespace ljd {
 // up takes the next `grab` samples off one grid-wide counter — so the lanes of a wave stay busy whatever the lengths of their paths
 // (one whole path per lane left a wave waiting for its longest path).  A sample's value depends on its pcg32 stream only.
 // counters[0..1]: bounce iterations (64 bit); counters[2]: the sample counter (zeroed before the launch).
-template <class Ft, int SPHERES, bool VIEWS>
+template <class Ft, int SPHERES, bool VIEWS, bool RAYS>
 __device__ __forceinline__ void volpath_body(const DScene &sc, const DPass &pass, uint32_t n_samples, uint32_t grab, uint32_t *counters, int stack, int lds_nodes, int lds_prims, int *spill) {
     const TreeView tv = stage_tree(sc, stack, lds_nodes, lds_prims, spill, gridDim.x * kBlock, blockIdx.x * kBlock + threadIdx.x);
     DevTracer<SPHERES> tr{tv, sc.spheres, sc.n_spheres};
@@ -51,7 +51,7 @@ __device__ __forceinline__ void volpath_body(const DScene &sc, const DPass &pass
                 if (!live && rank < left) {
                     sample = w_next + rank;
                     f3 rad;
-                    live = vol_path_begin_sample<Ft, VIEWS>(sc, pass, tr, sample, P, rad);
+                    live = vol_path_begin_sample<Ft, VIEWS, RAYS>(sc, pass, tr, sample, P, rad);
                     if (!live) finish(sample, rad, 0u);   // (the single-shot estimators of version 1 and 2)
                 }
                 w_next += n_dead < left ? n_dead : left;
@@ -75,10 +75,11 @@ __device__ __forceinline__ void volpath_body(const DScene &sc, const DPass &pass
 }
 // Instantiated per feature set of the scene (dshade.h: a scene of diffuse surfaces does not carry nine BSDFs), built for three waves per SIMD.
 // (The tracker's own state, not the BSDFs, is what fills the registers: 211 VGPRs unconstrained for diffuse-only against 224 for everything.)
-// (VIEWS: the pass is a batch of cameras, dshade.h)
-template <class Ft, int OCC, int SPHERES, bool VIEWS>
+// (VIEWS: the pass is a batch of cameras, dshade.h; RAYS: a table of rays or probes, dprobe.h — the sample counter sees its n * spp samples
+// as it sees the n_pixels * spp of a camera pass)
+template <class Ft, int OCC, int SPHERES, bool VIEWS, bool RAYS = false>
 __global__ void __launch_bounds__(kBlock, OCC) k_volpath(DScene sc, DPass pass, uint32_t n_samples, uint32_t grab, uint32_t *counters, int stack, int lds_nodes, int lds_prims, int *spill) {
-    volpath_body<Ft, SPHERES, VIEWS>(sc, pass, n_samples, grab, counters, stack, lds_nodes, lds_prims, spill);
+    volpath_body<Ft, SPHERES, VIEWS, RAYS>(sc, pass, n_samples, grab, counters, stack, lds_nodes, lds_prims, spill);
 }
 
 // ---------------------------------------------------------------- launcher
@@ -102,7 +103,8 @@ void launch_volpath(const DScene &sc, const DPass &pass, uint32_t n_samples, uin
     if (const char *e = getenv("LJ_TUNE_VOLPATH_SPHERES")) sph = cfg.spheres == 0 ? 0 : (atoi(e) == 1 ? 1 : sph);
     auto pick = [&](auto ft, auto occ_c) {
         using Ft = decltype(ft); constexpr int O = decltype(occ_c)::value;
-        if (pass.views) { if (sph == 0) launch(k_volpath<Ft, O, 0, true>); else if (sph == 2) launch(k_volpath<Ft, O, 2, true>); else launch(k_volpath<Ft, O, 1, true>); }
+        if (pass.ray_kind != RAY_SOURCE_NONE) { if (sph == 0) launch(k_volpath<Ft, O, 0, false, true>); else if (sph == 2) launch(k_volpath<Ft, O, 2, false, true>); else launch(k_volpath<Ft, O, 1, false, true>); }
+        else if (pass.views) { if (sph == 0) launch(k_volpath<Ft, O, 0, true>); else if (sph == 2) launch(k_volpath<Ft, O, 2, true>); else launch(k_volpath<Ft, O, 1, true>); }
         else if (sph == 0) launch(k_volpath<Ft, O, 0, false>); else if (sph == 2) launch(k_volpath<Ft, O, 2, false>); else launch(k_volpath<Ft, O, 1, false>);
     };
     // `plain`: the classic materials in constant colours under mesh lights (vol_cbox_teapot: diffuse walls, a rough dielectric teapot) — without the
@@ -111,6 +113,7 @@ void launch_volpath(const DScene &sc, const DPass &pass, uint32_t n_samples, uin
     if (v == 0) pick(FeatLambert{}, std::integral_constant<int, 3>{});
     else if (v == 3 && plain) pick(FeatClassicPlain{}, std::integral_constant<int, 3>{});
     else if (v == 3) pick(FeatClassic{}, std::integral_constant<int, 3>{});
+    else if (occ <= 2 && pass.ray_kind != RAY_SOURCE_NONE) launch(k_volpath<FeatAll, 2, 1, false, true>);
     else if (occ <= 2 && pass.views) launch(k_volpath<FeatAll, 2, 1, true>);
     else if (occ <= 2) launch(k_volpath<FeatAll, 2, 1, false>);
     else pick(FeatAll{}, std::integral_constant<int, 3>{});
