@@ -290,13 +290,14 @@ int lj_scene_update_geometry(lj_scene *scene, const LjSceneDesc *desc);
  * Blocking, ordered on the context's stream.  lj_get_stats after the call: render_ms = device time, generate_ms = host time, every
  * other field 0.
  *
- * Refit, rebuild or re-upload (measured, DESIGN.md section 3.10: 60 K - 66 K triangles, 16 spp, one MI355X): an update costs 4 - 5 ms, update
- * plus rebuild 12 - 15 ms, a re-upload 340 - 790 ms; a frame on the refitted tree takes 1.4 - 5.8 times the freshly built tree's time, on the
- * rebuilt tree 1.15 - 1.55 times.  So: refit alone for a scene with a leaf table (nothing else happens anyway) and for a pose that is
- * rendered for less than the rebuild's 8 - 10 ms; rebuild after the update whenever more than that is rendered per pose — it paid for
- * itself within one 16-spp frame in every case measured, at amplitude 0 too, because it also sheds what the first refit lost (the
- * clipping of the upload's split leaves); re-upload only for a pose that is rendered for seconds, where the last 15 - 55 % are worth
- * half a second of host time. */
+ * Refit, rebuild or re-upload (measured, DESIGN.md sections 3.10 and 3.12: 60 K - 66 K triangles, 16 spp, one MI355X): an update costs
+ * 4 - 5 ms, update plus rebuild 12 - 15 ms with either builder of lj_scene_rebuild_bvh_ex, a re-upload 340 - 790 ms; a frame on the refitted
+ * tree takes 1.4 - 5.7 times the freshly built tree's time, on the linear builder's tree 1.15 - 1.56 times, on LJ_BUILD_PLOC's 1.11 - 1.43
+ * times (5 - 8 % below the linear builder's on sponza, 0 - 4 % on disney_bsdf).  So: refit alone for a scene with a leaf table (nothing else
+ * happens anyway) and for a pose that is rendered for less than the rebuild's 8 - 10 ms; rebuild after the update whenever more than that is
+ * rendered per pose — it paid for itself within one 16-spp frame in every case measured, at amplitude 0 too, because it also sheds what the
+ * first refit lost (the clipping of the upload's split leaves) — and with LJ_BUILD_PLOC where triangle sizes are mixed, as it costs no more;
+ * re-upload only for a pose that is rendered for seconds, where the last 11 - 43 % are still worth half a second of host time. */
 int lj_scene_rebuild_bvh(lj_scene *scene);
 /* Of the scene's last lj_scene_rebuild_bvh (zeros before the first): rebuilt 1 or 0 (the no-op above); primitives, leaves, nodes and
  * depths of the trees as they stand; build_ms = the device's linear BVH (boxes, codes, sort, hierarchy, fit) and its readback,
@@ -310,6 +311,30 @@ int lj_get_rebuild_stats(const lj_scene *scene, LjRebuildStats *out);
  * (0 for n = 0); nodes_out may be null to ask for it, else capacity (in nodes) must hold them. */
 typedef struct LjBinaryNode { float lo[3], hi[3]; int32_t left, right, first, count; } LjBinaryNode;   /* 40 bytes */
 int lj_bvh_build_query(lj_context *ctx, int64_t n, const float *boxes, int32_t *order_out, LjBinaryNode *nodes_out, int64_t capacity, int64_t *n_nodes);
+
+/* ---- the same with a choice of builder
+ * LJ_BUILD_LBVH is lj_scene_rebuild_bvh itself, byte for byte.  LJ_BUILD_PLOC replaces the radix tree by parallel locally-ordered
+ * clustering (Meister & Bittner, TVCG 2018) over the same Morton order: in rounds, every cluster merges with the neighbour within `radius`
+ * positions that gives the smallest union box, until one is left; a cluster of at most four primitives becomes a leaf.  It looks at the boxes
+ * it joins, which the linear BVH never does, so its trees are cheaper to traverse where triangle sizes are mixed; it takes 50 - 70 rounds where
+ * the radix tree takes one launch, and was no slower per rebuild where measured (its trees have fewer leaves to emit).  radius: PLOC only; <= 0: 8; at most 32.  args NULL or zeroed: lj_scene_rebuild_bvh.
+ * Everything lj_scene_rebuild_bvh documents holds: the no-op for a scene with a leaf table and an empty one, every check before the first
+ * write, blocking, LjStats and LjRebuildStats (build_ms covers the clustering), LJ_TUNE_* read again.  Further refusals:
+ * LJ_ERR_INVALID_ARG for an unknown builder or a radius above 32; LJ_ERR_UNSUPPORTED when 256 rounds of clustering leave more than 1024
+ * clusters (the measured scenes take 19 - 25 to get there; boxes nested inside each other along the whole Morton curve would not) — use the
+ * linear builder for such a scene; nothing is written. */
+enum { LJ_BUILD_LBVH = 0, LJ_BUILD_PLOC = 1 };
+typedef struct LjRebuildArgs { int32_t builder; int32_t radius; } LjRebuildArgs;
+int lj_scene_rebuild_bvh_ex(lj_scene *scene, const LjRebuildArgs *args);
+/* lj_bvh_build_query with the builder of args.  With LJ_BUILD_PLOC, order_out is the primitives in the depth-first order of the
+ * cluster tree (a leaf still holds order_out[first .. first + count)). */
+int lj_bvh_build_query_ex(lj_context *ctx, const LjRebuildArgs *args, int64_t n, const float *boxes, int32_t *order_out,
+                          LjBinaryNode *nodes_out, int64_t capacity, int64_t *n_nodes);
+/* Of the scene's last rebuild by either call (zeros before the first, and after the no-op): the builder and radius that ran (radius 0 for
+ * LJ_BUILD_LBVH), the rounds of clustering in all, how many of them ran in the single-workgroup tail launch, and the host time of the builder's
+ * launches from the centroid bounds to the last round, which build_ms includes. */
+typedef struct LjBuildStats { int32_t builder, radius; uint64_t rounds, tail_rounds; double cluster_ms; } LjBuildStats;
+int lj_get_build_stats(const lj_scene *scene, LjBuildStats *out);
 
 /* Readback of an acceleration structure as it stands on the device, for tests: which = 0 the BVH4 (128-byte DNode4 records), 1 the BVH8
  * (80-byte DNode8 records, packed whatever their stride on the device), 2 a tiny scene's leaf table (32-byte DScanLeaf records; none for

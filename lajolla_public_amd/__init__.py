@@ -200,25 +200,45 @@ class Scene:
         positions / radii (HostScene.positions_view()); everything derived from them is re-derived and the BVHs are refitted on the device,
         nothing else is rebuilt (lj_scene_update_geometry).  Later renders and queries see the new geometry, bit-identical to a fresh
         Scene of the same description.  A refused update (LajollaError, LJ_ERR_INVALID_ARG) leaves the scene as it was.
-        rebuild=True: rebuild_bvh() after the update."""
+        rebuild=True: rebuild_bvh() after the update; rebuild="lbvh" or "ploc": rebuild_bvh(builder=rebuild)."""
         lib = load_library()
         desc_ptr = host_scene_or_desc.desc_ptr if isinstance(host_scene_or_desc, HostScene) else C.pointer(host_scene_or_desc)
+        if isinstance(rebuild, str):
+            _builder_args(rebuild, None)   # (a misspelt builder is refused before the update)
         _check(lib.lj_scene_update_geometry(self._h, desc_ptr))
-        if rebuild:
+        if isinstance(rebuild, str):
+            _check(lib.lj_scene_rebuild_bvh_ex(self._h, C.byref(_builder_args(rebuild, None))))
+        elif rebuild:
             _check(lib.lj_scene_rebuild_bvh(self._h))
         info = LjSceneInfo()
         _check(lib.lj_scene_info(self._h, C.byref(info)))
         self.info = info
 
-    def rebuild_bvh(self):
-        """Rebuild both trees on the device for the geometry as it stands there (lj_scene_rebuild_bvh): a linear BVH in place of the
-        refitted trees.  Hits and per-sample radiance do not change.  A leaf-scan scene (at most 32 leaves and 256 primitives) and an
-        empty scene are left as they are (rebuild_stats(scene).rebuilt == 0).  LJ_TUNE_* are read again, as at upload."""
+    def rebuild_bvh(self, builder="lbvh", radius=None):
+        """Rebuild both trees on the device for the geometry as it stands there (lj_scene_rebuild_bvh_ex): builder="lbvh", a linear BVH in
+        place of the refitted trees (lj_scene_rebuild_bvh itself), or "ploc", locally-ordered clustering with the given search radius (None:
+        8; at most 32).  Hits and per-sample radiance do not change.  A leaf-scan scene (at most 32 leaves and 256 primitives) and an empty
+        scene are left as they are (rebuild_stats(scene).rebuilt == 0).  LJ_TUNE_* are read again, as at upload."""
         lib = load_library()
-        _check(lib.lj_scene_rebuild_bvh(self._h))
+        if builder == "lbvh" and radius is None:
+            _check(lib.lj_scene_rebuild_bvh(self._h))
+        else:
+            _check(lib.lj_scene_rebuild_bvh_ex(self._h, C.byref(_builder_args(builder, radius))))
         info = LjSceneInfo()
         _check(lib.lj_scene_info(self._h, C.byref(info)))
         self.info = info
+
+
+_BUILDERS = {"lbvh": _abi.LJ_BUILD_LBVH, "ploc": _abi.LJ_BUILD_PLOC}
+
+
+def _builder_args(builder, radius):
+    """LjRebuildArgs of a builder's name (or its LJ_BUILD_* number, handed on as it is) and a radius"""
+    if isinstance(builder, str):
+        if builder not in _BUILDERS:
+            raise ValueError("builder must be one of %s, not %r" % (sorted(_BUILDERS), builder))
+        builder = _BUILDERS[builder]
+    return _abi.LjRebuildArgs(int(builder), 0 if radius is None else int(radius))
 
 
 def read_bvh(scene, which):
@@ -240,18 +260,30 @@ def rebuild_stats(scene):
     return st
 
 
+def build_stats(scene):
+    """LjBuildStats of the scene's last rebuild_bvh(): the builder and radius that ran, its rounds of clustering (zeros before the first)."""
+    st = _abi.LjBuildStats()
+    _check(load_library().lj_get_build_stats(scene._h, C.byref(st)))
+    return st
+
+
 BINARY_NODE = np.dtype([("lo", np.float32, 3), ("hi", np.float32, 3), ("left", np.int32), ("right", np.int32), ("first", np.int32), ("count", np.int32)])
 
 
-def bvh_build_query(ctx, boxes):
-    """The device's linear BVH over boxes (n, 2, 3) float32 — lo, hi — (lj_bvh_build_query, a test hook): (order, nodes); order[i] is the
-    box at sorted position i, nodes a BINARY_NODE array, breadth-first from the root."""
+def bvh_build_query(ctx, boxes, builder="lbvh", radius=None):
+    """The device's binary tree over boxes (n, 2, 3) float32 — lo, hi — (lj_bvh_build_query_ex, a test hook), by the linear builder or by
+    "ploc" with its search radius: (order, nodes); order[i] is the box at position i of the leaves' order, nodes a BINARY_NODE array,
+    breadth-first from the root."""
     boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 2, 3)
     n = boxes.shape[0]
     order = np.zeros(n, np.int32)
     nodes = np.zeros(max(2 * n, 1), BINARY_NODE)
     got = C.c_int64()
-    _check(load_library().lj_bvh_build_query(ctx._h, n, boxes.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p), nodes.ctypes.data_as(C.c_void_p), nodes.size, C.byref(got)))
+    lib, ptr = load_library(), lambda a: a.ctypes.data_as(C.c_void_p)
+    if builder == "lbvh" and radius is None:
+        _check(lib.lj_bvh_build_query(ctx._h, n, ptr(boxes), ptr(order), ptr(nodes), nodes.size, C.byref(got)))
+    else:
+        _check(lib.lj_bvh_build_query_ex(ctx._h, C.byref(_builder_args(builder, radius)), n, ptr(boxes), ptr(order), ptr(nodes), nodes.size, C.byref(got)))
     return order, nodes[:got.value].copy()
 
 

@@ -183,6 +183,17 @@ class LjRebuildStats(C.Structure):
                 ("depth4", C.c_int32), ("depth8", C.c_int32), ("build_ms", C.c_double), ("emit_ms", C.c_double), ("refit_ms", C.c_double)]
 
 
+LJ_BUILD_LBVH, LJ_BUILD_PLOC = 0, 1
+
+
+class LjRebuildArgs(C.Structure):
+    _fields_ = [("builder", C.c_int32), ("radius", C.c_int32)]
+
+
+class LjBuildStats(C.Structure):
+    _fields_ = [("builder", C.c_int32), ("radius", C.c_int32), ("rounds", C.c_uint64), ("tail_rounds", C.c_uint64), ("cluster_ms", C.c_double)]
+
+
 class LjBinaryNode(C.Structure):
     _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("left", C.c_int32), ("right", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
 
@@ -297,6 +308,9 @@ SYMBOLS = [
     ("lj_scene_rebuild_bvh", C.c_int, [C.c_void_p]),
     ("lj_get_rebuild_stats", C.c_int, [C.c_void_p, C.POINTER(LjRebuildStats)]),
     ("lj_bvh_build_query", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("lj_scene_rebuild_bvh_ex", C.c_int, [C.c_void_p, C.POINTER(LjRebuildArgs)]),
+    ("lj_bvh_build_query_ex", C.c_int, [C.c_void_p, C.POINTER(LjRebuildArgs), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("lj_get_build_stats", C.c_int, [C.c_void_p, C.POINTER(LjBuildStats)]),
     ("lj_render_views", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p]),
     ("lj_render_views_device", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.c_void_p, C.c_void_p]),
     ("lj_render_features", C.c_int, [C.c_void_p, C.POINTER(LjRenderArgs), C.c_int32, C.POINTER(LjCamera), C.POINTER(LjFeatureBuffers)]),

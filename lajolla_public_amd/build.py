@@ -26,7 +26,7 @@ ORACLE_LIB = os.path.join(ROOT, "oracle", "_build", "liblj_oracle_asan.so" if _S
 TWIN_LIB = os.path.join(ROOT, "tests", "twin", "_build", "libljtwin_asan.so" if _SAN else "libljtwin.so")
 
 HOST_SOURCES = ["host/api_host.cpp", "host/scene_xml.cpp", "host/mesh_io.cpp", "host/image_io.cpp", "host/jpeg_decode.cpp", "host/exr_decode.cpp", "host/png_decode.cpp", "host/tga_bmp_decode.cpp", "host/flatten.cpp", "host/bvh.cpp"]
-HIP_SOURCES = ["device/kernels.hip", "device/shade_rays.hip", "device/volpath.hip", "device/extend.hip", "device/extend8.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip", "device/adaptive.hip", "device/rebuild.hip"]
+HIP_SOURCES = ["device/kernels.hip", "device/shade_rays.hip", "device/volpath.hip", "device/extend.hip", "device/extend8.hip", "device/api_device.hip", "device/render.hip", "device/queries.hip", "device/mega.hip", "device/group.hip", "device/tile.hip", "device/refit.hip", "device/features.hip", "device/denoise.hip", "device/adaptive.hip", "device/rebuild.hip", "device/ploc.hip"]
 ARCH = "gfx950"
 
 
@@ -339,6 +339,25 @@ def build_twin_rebuild(verbose=True):
     return TWIN_REBUILD_LIB
 
 
+TWIN_PLOC_LIB = os.path.join(ROOT, "tests", "twin_ploc", "_build", "libljtwinploc_asan.so" if _SAN else "libljtwinploc.so")
+
+
+def build_twin_ploc(verbose=True):
+    """Host twin of lj_scene_rebuild_bvh_ex with LJ_BUILD_PLOC (the rule of device/dploc.h, compact_ploc_tree, and the twin of the rebuild it
+    includes) for the CPU-side tests; the flags of build_twin_rebuild."""
+    src = os.path.join(ROOT, "tests", "twin_ploc", "twin_ploc.cpp")
+    if not os.path.exists(src):
+        return None
+    os.makedirs(os.path.dirname(TWIN_PLOC_LIB), exist_ok=True)
+    deps = [src, os.path.join(ROOT, "tests", "twin_rebuild", "twin_rebuild.cpp"), os.path.join(ROOT, "tests", "twin_refit", "twin_refit.cpp")] + _headers() + [os.path.join(CSRC, s) for s in ("host/flatten.cpp", "host/bvh.cpp")]
+    if _stale(TWIN_PLOC_LIB, deps):
+        if verbose:
+            print("[build] compiling the host twin of the PLOC rebuild (CPU-side tests only)", file=sys.stderr)
+        _run(["g++", "-std=c++17", "-O1" if _SAN else "-O2", "-ffp-contract=off"] + _SAN_FLAGS + _host_fma_flag() + ["-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+              "-o", TWIN_PLOC_LIB, src, os.path.join(CSRC, "host/flatten.cpp"), os.path.join(CSRC, "host/bvh.cpp"), "-lpthread"])
+    return TWIN_PLOC_LIB
+
+
 TWIN_RAYS_LIB = os.path.join(ROOT, "tests", "twin_rays", "_build", "libljtwinrays_asan.so" if _SAN else "libljtwinrays.so")
 
 
@@ -381,5 +400,6 @@ if __name__ == "__main__":
         build_twin_denoise()
         build_twin_adaptive()
         build_twin_rebuild()
+        build_twin_ploc()
         build_twin_rays()
     print(LIB)

@@ -82,7 +82,14 @@ struct RebuildWork { void *boxes, *bounds, *codes, *codes_sorted; int32_t *vals,
 RebuildWork rebuild_carve(void *workspace, int n, hipStream_t s);
 size_t rebuild_node_bytes();
 void launch_rebuild_prim_boxes(const DPrim *leaf_prims, int n_leaf_prims, const DSphere *spheres, const RebuildWork &w, int n, hipStream_t s);
+void launch_rebuild_order(const RebuildWork &w, int n, hipStream_t s);   // the first half of launch_rebuild: w.order and the sorted codes
 void launch_rebuild(const RebuildWork &w, int n, hipStream_t s);
+// ploc.hip: the clustering of lj_scene_rebuild_bvh_ex (dploc.h) over the order that launch_rebuild_order leaves; its nodes go to w.nodes, its
+// own scratch is a PlocWork carved behind the RebuildWork in the same workspace.  ploc_carve(null, n).bytes is the size to add.
+struct PlocWork { void *box[2]; int32_t *id[2], *count[2], *nn; uint8_t *flags; void *counts, *offsets; uint32_t *total; size_t bytes; };
+struct PlocRun { uint64_t rounds, tail_rounds; bool finished; };
+PlocWork ploc_carve(void *workspace, int n);
+PlocRun launch_ploc(const RebuildWork &w, const PlocWork &p, int n, int radius, int tail, uint32_t *host_word, hipStream_t s);
 }
 
 using lj::LjError;
@@ -187,6 +194,7 @@ struct lj_scene {
     LjFeatureStats feature_stats{};   // of the last lj_render_features* call; zeros after any other render
     LjAdaptiveStats adaptive_stats{};   // of the last lj_render_adaptive* call; zeros after any other render
     LjRebuildStats rebuild_stats{};   // of the last lj_scene_rebuild_bvh
+    LjBuildStats build_stats{};       // of the last lj_scene_rebuild_bvh or lj_scene_rebuild_bvh_ex: which builder ran, and its rounds
 };
 
 inline void set_device(lj_context *ctx) { HIP_CHECK(hipSetDevice(ctx->device)); }

@@ -124,8 +124,8 @@ void launch_rebuild_prim_boxes(const DPrim *leaf_prims, int n_leaf_prims, const 
     hipLaunchKernelGGL(k_rebuild_prim_boxes, dim3(rebuild_grid(n_leaf_prims)), dim3(kRebuildBlock), 0, s, leaf_prims, n_leaf_prims, spheres, (RefitBox *)w.boxes, n);
 }
 
-// From w.boxes[0 .. n): w.order (sorted position -> primitive) and, for n >= 2, the n - 1 nodes of the radix tree with their boxes
-void launch_rebuild(const RebuildWork &w, int n, hipStream_t s) {
+// From w.boxes[0 .. n): the sorted codes in w.codes_sorted and w.order (sorted position -> primitive); ploc.hip starts from these too
+void launch_rebuild_order(const RebuildWork &w, int n, hipStream_t s) {
     if (n <= 0) return;
     const RefitBox *boxes = (const RefitBox *)w.boxes;
     unsigned long long *bounds = (unsigned long long *)w.bounds;
@@ -135,7 +135,14 @@ void launch_rebuild(const RebuildWork &w, int n, hipStream_t s) {
     hipLaunchKernelGGL(k_rebuild_codes, dim3(rebuild_grid(n)), dim3(kRebuildBlock), 0, s, boxes, n, bounds, (uint64_t *)w.codes, w.vals);
     size_t temp = w.sort_temp_bytes;
     HIP_CHECK(rocprim::radix_sort_pairs(w.sort_temp, temp, (uint64_t *)w.codes, (uint64_t *)w.codes_sorted, w.vals, w.order, (unsigned int)n, 0, 63, s));
+}
+
+// From w.boxes[0 .. n): w.order and, for n >= 2, the n - 1 nodes of the radix tree with their boxes
+void launch_rebuild(const RebuildWork &w, int n, hipStream_t s) {
+    if (n <= 0) return;
+    launch_rebuild_order(w, n, s);
     if (n < 2) return;
+    const RefitBox *boxes = (const RefitBox *)w.boxes;
     HIP_CHECK(hipMemsetAsync(w.arrived, 0, (size_t)(n - 1) * 4, s));
     hipLaunchKernelGGL(k_rebuild_hierarchy, dim3(rebuild_grid(n - 1)), dim3(kRebuildBlock), 0, s, (const uint64_t *)w.codes_sorted, n, (RebuildNode *)w.nodes, w.parent);
     hipLaunchKernelGGL(k_rebuild_fit, dim3(rebuild_grid(n)), dim3(kRebuildBlock), 0, s, (RebuildNode *)w.nodes, boxes, w.order, w.parent, (unsigned int *)w.arrived, n);

@@ -513,4 +513,58 @@ std::vector<BinaryNode> compact_radix_tree(const void *raw_bytes, const float *b
     return out;
 }
 
+std::vector<BinaryNode> compact_ploc_tree(const void *raw_bytes, const float *boxes, const int32_t *order, int64_t n, std::vector<int32_t> &order_out) {
+    std::vector<BinaryNode> out;
+    order_out.clear();
+    if (n <= 0) return out;
+    const BinaryNode *raw = (const BinaryNode *)raw_bytes;   // (ljd::RebuildNode, children coded as drebuild.h says)
+    auto single = [&](int32_t pos, int32_t first) {
+        BinaryNode b{};
+        for (int k = 0; k < 3; k++) { b.lo[k] = boxes[6 * (size_t)order[pos] + k]; b.hi[k] = boxes[6 * (size_t)order[pos] + 3 + k]; }
+        b.left = b.right = -1; b.first = first; b.count = 1;
+        return b;
+    };
+    if (n == 1) { order_out.push_back(order[0]); out.push_back(single(0, 0)); return out; }
+    // a node's children were clustered before it: every inner child has a lower index, so the records cannot form a cycle; with every
+    // node but the root and every position referenced once, and every count the sum below it, they are one tree over all n
+    const int64_t n_raw = n - 1;
+    const char *bad = "the device's cluster tree is not a tree over the primitives";
+    std::vector<uint8_t> node_refs((size_t)n_raw, 0), pos_refs((size_t)n, 0);
+    for (int64_t i = 0; i < n_raw; i++) {
+        int64_t below = 0;
+        for (const int32_t k : {raw[i].left, raw[i].right}) {
+            if (k >= 0) { if (k >= i || node_refs[k]++) throw LjError(LJ_ERR_INTERNAL, bad); below += raw[k].count; }
+            else { if (~k >= n || pos_refs[~k]++) throw LjError(LJ_ERR_INTERNAL, bad); below += 1; }
+        }
+        if (raw[i].count != below) throw LjError(LJ_ERR_INTERNAL, bad);
+    }
+    if (raw[n_raw - 1].count != n) throw LjError(LJ_ERR_INTERNAL, bad);   // (then no other node is unreferenced, and no position)
+    // left-first depth-first walk from the root: the primitives in the order the leaves hold them
+    std::vector<int32_t> first((size_t)n_raw, 0), where((size_t)n, 0), stack{(int32_t)(n_raw - 1)};
+    order_out.reserve((size_t)n);
+    while (!stack.empty()) {
+        const int32_t k = stack.back(); stack.pop_back();
+        if (k < 0) { where[~k] = (int32_t)order_out.size(); order_out.push_back(order[~k]); continue; }
+        first[k] = (int32_t)order_out.size();
+        stack.push_back(raw[k].right); stack.push_back(raw[k].left);
+    }
+    if ((int64_t)order_out.size() != n) throw LjError(LJ_ERR_INTERNAL, bad);
+    // breadth-first numbering from node 0, as compact_radix_tree numbers its output
+    std::vector<int32_t> source{(int32_t)(n_raw - 1)};
+    out.push_back(raw[n_raw - 1]);
+    for (size_t h = 0; h < out.size(); h++) {
+        if (source[h] < 0) continue;
+        const int32_t kids[2] = {out[h].left, out[h].right};
+        out[h].first = first[source[h]];
+        if (out[h].count <= 4) { out[h].left = out[h].right = -1; continue; }
+        for (int c = 0; c < 2; c++) {
+            const int32_t k = kids[c];
+            (c == 0 ? out[h].left : out[h].right) = (int32_t)out.size();
+            source.push_back(k);
+            if (k < 0) out.push_back(single(~k, where[~k])); else out.push_back(raw[k]);
+        }
+    }
+    return out;
+}
+
 } // namespace lj

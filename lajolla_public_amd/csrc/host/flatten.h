@@ -98,6 +98,13 @@ void emit_wide(const std::vector<BinaryNode> &tree, const std::vector<int> &orde
 // a node of at most four primitives is a leaf; n == 1: one leaf), compacted breadth-first from the root (root = 0).
 // raw: n - 1 records of 40 bytes (ljd::RebuildNode); boxes: float[6] per primitive; order: sorted position -> primitive.
 std::vector<BinaryNode> compact_radix_tree(const void *raw, const float *boxes, const int32_t *order, int64_t n);
+// The same of the device's cluster tree (device/dploc.h: raw[n - 2] is the root of the n - 1 nodes, which carry no ranges and may be n
+// deep): an iterative left-first depth-first walk from the root gives order_out[p], the primitive at depth-first position p; a node of at
+// most four primitives becomes a leaf over its positions with its own box, a single primitive a leaf with the primitive's box (an inner node carries the
+// range of positions below it too); nodes are numbered breadth-first from node 0, so everything downstream of compact_radix_tree runs unchanged on (the result, order_out).  Every child
+// index is range-checked, every count must be the sum of its children's, and every node and position must be reached once: otherwise
+// LJ_ERR_INTERNAL.
+std::vector<BinaryNode> compact_ploc_tree(const void *raw, const float *boxes, const int32_t *order, int64_t n, std::vector<int32_t> &order_out);
 
 // lj_scene_rebuild_bvh, host part: from the compacted binary tree over the scene's global primitives (tree leaves index `order`, which
 // holds global primitive ids, each once), the trees, leaf order, leaf-ordered primitives (from prev's), level tables and depths of the
