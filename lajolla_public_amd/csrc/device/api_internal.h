@@ -1,8 +1,11 @@
-// Internals shared by the C-ABI translation units that own the GPU (api_device.hip: context and scene lifetime, upload, geometry
-// update, ray queries and the extern "C" render entry points; render.hip: render plans and the five render drivers behind run_render;
-// queries.hip: the batched per-object queries): HIP error boundary, device buffers, the small helpers those files share, the context
-// and scene objects behind the opaque handles of include/lajolla_hip.h, the kernel launchers of kernels.hip (shade, tail, resolve),
-// extend.hip (extend, aux, ray queries and their launch plan) and the other kernel files, and what render.hip offers the entry points.
+// Internals shared by the translation units that own the GPU.  The entry points, one file per family: api_device.hip (context and scene
+// lifetime, upload, camera, BVH read-back, the plain renders, batched ray queries), api_geometry.hip (geometry update, refit, the two BVH
+// builders, the build query), api_film.hip (lj_render_features*, lj_render_adaptive*), api_denoise.hip (lj_denoise*) and api_rays.hip
+// (tables of rays and probes).  Behind them render.hip (render plans, run_render and its five drivers) and queries.hip (the batched
+// per-object queries); the kernel files include this header for their launchers' declarations.
+// In order: the launchers of every kernel file; the HIP error boundary, device buffers and developer switches; the context and scene
+// objects behind the opaque handles of include/lajolla_hip.h; and what render.hip, api_device.hip and api_geometry.hip offer the
+// other files.  The call sequences that the entry points share are in api_calls.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../host/api_common.h"
@@ -175,6 +178,9 @@ struct lj_context {
     hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr, ev_a2 = nullptr;
     DevBuf rebuild_ws;   // lj_scene_rebuild_bvh / lj_bvh_build_query: the workspace of rebuild.hip
 };
+// the context's timing events (hipEventCreate: they time), which lj_context_create and lj_context_destroy both walk
+static constexpr hipEvent_t lj_context::*kTimingEvents[] = {&lj_context::ev_begin, &lj_context::ev_end, &lj_context::ev_k0, &lj_context::ev_k1, &lj_context::ev_f0, &lj_context::ev_f1,
+    &lj_context::ev_f2, &lj_context::ev_d0, &lj_context::ev_d1, &lj_context::ev_a0, &lj_context::ev_a1, &lj_context::ev_a2};
 
 struct lj_scene {
     lj_context *ctx = nullptr;
@@ -232,3 +238,12 @@ RenderPlan make_rays_plan(lj_scene *sc, const LjRenderArgs *a, int64_t n);
 void run_render(lj_scene *sc, const RenderPlan &plan, float *rgb_dev, float *samples_host, hipStream_t stream, bool timing);
 void run_probe_rays(lj_scene *sc, const RenderPlan &plan, float *rays_host, hipStream_t stream);   // the first segments of a probes plan, pass by pass: rays_host[list position * spp + s][6]
 int *ensure_spill(lj_context *ctx, int levels, uint32_t grid);
+
+// ---- api_device.hip and api_geometry.hip (`me`, in every entry-point file: the extern "C" function's name, which its error messages begin with)
+bool scene_is_live(const lj_scene *sc);   // an uploaded scene of this process that was not destroyed
+void install_trees(lj_scene *sc, hipStream_t s);
+void render_frames(lj_scene *scene, RenderPlan plan, const std::vector<ljd::DCamera> &views, float *const dst[6], bool on_device, hipStream_t caller, bool timing);
+std::vector<ljd::DCamera> view_table(const lj_scene *scene, int32_t n_views, const LjCamera *views, const std::string &me);
+void alloc_refit_tables(lj_scene *scene, hipStream_t s);
+void refit_launches(lj_scene *scene, hipStream_t s);
+void read_back_nodes(lj_scene *scene, hipStream_t s);

@@ -1,4 +1,5 @@
-// The render path behind the entry points of api_device.hip: render plans (which pixels, how many samples, which cameras) and run_render,
+// The render path behind the entry points of the api_*.hip files (api_device.hip: the plain renders; api_film.hip: features and adaptive
+// rounds; api_rays.hip: tables of rays and probes): render plans (which pixels, how many samples, which cameras or rays) and run_render,
 // which hands a plan to one of five drivers — render_aux, render_tiles, render_volpath, render_mega, render_wavefront — one per kernel plan.
 // The drivers share the pass loop (pass_at), the end of a pass (finish_pass), the render timer (close_timer) and the workspace of the context.
 //
