@@ -177,8 +177,8 @@ int lj_scene_upload(lj_context *ctx, const LjSceneDesc *desc, lj_scene **out) {
             for (const auto &m : F.materials) { kinds |= 1u << m.kind; for (int t = 0; t < 12; t++) textured = textured || m.tex[t].kind != 0; }
             for (const auto &l : F.lights) sphere_lights = sphere_lights || (l.kind == 0 && l.is_sphere);
             sc->feat_kinds = kinds; sc->feat_textured = textured; sc->feat_envmap = F.envmap_light_id >= 0; sc->feat_sphere_lights = sphere_lights;
-            sc->scfg.variant = ljd::shade_variant(kinds, textured, F.envmap_light_id >= 0, sphere_lights);
-            sc->scfg.variant = std::max(sc->scfg.variant, env_int("LJ_TUNE_SHADE_VARIANT", sc->scfg.variant));
+            // (LJ_TUNE_SHADE_VARIANT: a larger feature set than the scene needs, taken only if it covers the scene)
+            sc->scfg.variant = ljd::shade_variant(kinds, textured, F.envmap_light_id >= 0, sphere_lights, env_int("LJ_TUNE_SHADE_VARIANT", -1));
             if (sc->scfg.smem == 0) sc->scfg.variant = ljd::kShadeVariantAll;   // tables too large to stage: one instantiation serves that case
         }
         ctx->live_scenes++;

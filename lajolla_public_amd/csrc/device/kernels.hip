@@ -424,8 +424,11 @@ ShadeConfig shade_config(size_t n_prims, size_t n_materials, size_t n_lights, si
     return c;
 }
 
-// shade_variant() returns the first (smallest) feature set that covers a scene
-int shade_variant(uint32_t kinds, bool textured, bool envmap, bool sphere_lights) {
+// shade_variant() returns the first (smallest) feature set that covers a scene — or `preferred`, where that is one and covers the scene too.
+// (The sets are not ordered by what they hold: FeatDisney, 4, has no roughplastic.  A path on a Material alternative its kernel lacks gets
+// no slot in the kernel's sort, so a set that does not cover the scene must never run.)
+int shade_variant(uint32_t kinds, bool textured, bool envmap, bool sphere_lights, int preferred) {
+    if (preferred >= 0 && preferred < kNumShadeVariants && variant_covers(preferred, kinds, textured, envmap, sphere_lights)) return preferred;
     for (int v = 0; v < kNumShadeVariants; v++) if (variant_covers(v, kinds, textured, envmap, sphere_lights)) return v;
     return kNumShadeVariants - 1;
 }

@@ -255,6 +255,15 @@ class Twin:
         return occ.astype(bool)
 
 
+def plan_ran(st, plan):
+    """Whether the kernel plan "mega", "wavefront" or "volpath" produced the LjStats `st` of a render."""
+    if plan == "mega":
+        return st.mega_launches >= 1 and st.shade_launches == 0
+    if plan == "wavefront":
+        return st.mega_launches == 0 and st.shade_launches > 0
+    return st.mega_launches == 0 and st.shade_launches == 0 and st.wavefront_steps >= 1   # volpath: one launch per pass
+
+
 def scene_path(name):
     return {"cbox": os.path.join(SCENES, "cbox", "cbox.xml"), "veach_mi": os.path.join(SCENES, "veach_mi", "mi.xml"),
             "disney_bsdf": os.path.join(SCENES, "disney_bsdf_test", "disney_bsdf.xml"), "sponza": os.path.join(SCENES, "sponza", "sponza.xml")}[name]

@@ -12,7 +12,7 @@ import pytest
 
 import lajolla_public_amd as lj
 from lajolla_public_amd import _abi
-from helpers import GpuQueries
+from helpers import GpuQueries, plan_ran
 from views_common import W, H, cameras_for, derived_cameras, scene_file, set_host_camera
 from features_common import FEATURES, HETVOL, compose_samples, disney_scene, reduce64, sum_bound, variance64
 
@@ -76,14 +76,6 @@ class Bench:
 @pytest.fixture(scope="module")
 def bench():
     return Bench()
-
-
-def plan_ran(st, plan):
-    if plan == "mega":
-        return st.mega_launches >= 1 and st.shade_launches == 0
-    if plan == "wavefront":
-        return st.mega_launches == 0 and st.shade_launches > 0
-    return st.mega_launches == 0 and st.shade_launches == 0 and st.wavefront_steps >= 1   # volpath: one launch per pass
 
 
 def check_against_composition(ex, spp, want_crossings=False):
